@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """bench.py -- `Prover::prove(claim, aet)` on MI355X, BASELINE.json's metric (trace-cells/s in prove()).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--log2-rows 20] [--data real|synthetic] [--ldt fri|stir|auto]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--log2-rows 20] [--data real|synthetic] [--ldt fri|stir|auto] [--full]
+                    [--dump-outputs DIR]
 
 Default (`--data real`): BASELINE.json configs[1] for real -- the reference's prove_fib program
 (triton-dev-util/src/example_programs.rs:6-38) is run for 2^20 - 17 cycles, and ONE STEP is the whole of
@@ -11,14 +12,21 @@ extend (aux table), aux LDE, hashing + Merkle, AIR / quotient codeword, quotient
 combination, DEEP, the low-degree test, the openings, the proof's encoding -- through the C++ host
 (triton_vm_amd/host/triton_host.cpp, `triton_vm::prove_execution`) over the C ABI.  Stark::default() parameters with
 LdtChoice::Fri (what BASELINE.json's configurations name; the STIR that Stark::default() picks by itself at this size is
-measured beside it).  The proof of the last timed step is put through Verifier::verify before the line is printed.
+measured beside it, with --full).  With --full the proof of the last timed step is put through Verifier::verify before the line is
+printed.
 
 What is OUTSIDE the timed region: running the program (the VM is host work in the reference too and not part of
 `prove`; here the oracle-side VM, oracle/vm, stands in for the Rust VM -- workload generation, not a product path) and
 the one-time upload of the execution trace: the timed steps read a DEVICE-RESIDENT trace (inputs resident in HBM when the
 timed region starts); the same step from host arrays (327 MB over PCIe inside the step) is reported as
 `pcie_inclusive`.  `--data synthetic` times the hot path alone on random tables (rounds 1-2's headline; kept as the
-`synthetic_hot_path` key of the default run).
+`synthetic_hot_path` key of a --full run).
+
+A plain run sets up, warms up, times the K steps and prints the line: metric, value, unit, higher_is_better, dtype, ms_per_step
+(milliseconds per timed step) and the configuration.  Everything else runs only with --full: verifying the last proof, the per-stage
+profile, the roofline kernels timed on their own, and on one GPU the extras (pcie_inclusive, the other low-degree test, exact AIR,
+the synthetic hot path, eight lockstep ranks) and the CPU baseline.  --dump-outputs DIR writes the proof words of the last timed
+step to DIR/proof_words.npy (dump_outputs), so that two builds can be compared word for word on the same seeded inputs.
 
 metric = padded_rows * 652 / seconds per step (652 = 379 main + 3 * 91 aux base-field words per row).
 
@@ -593,6 +601,27 @@ def hot_kernel_timings(ctx, params):
     return sum(lde_ms) / 3, sum(hash_ms) / 3, rows
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(directory, proof_words):
+    """--dump-outputs: the proof words the last timed step handed back, as DIR/proof_words.npy -- float64 of shape (words, 2), every
+    u64 word split into its low and high 32 bits (both exact in a float64).  The inputs are seeded, so two builds given the same
+    arguments can be compared word for word.  Were it ever larger than 64 MB, a fixed seeded sample of the words is written instead,
+    with their indices in DIR/proof_words_index.npy."""
+    import numpy as np
+
+    os.makedirs(directory, exist_ok=True)
+    words = np.asarray(proof_words, dtype=np.uint64)
+    halves = np.stack([words & np.uint64(0xFFFFFFFF), words >> np.uint64(32)], axis=1).astype(np.float64)
+    if halves.nbytes > DUMP_LIMIT_BYTES:
+        rows = DUMP_LIMIT_BYTES // 2 // halves[0].nbytes
+        index = np.sort(np.random.default_rng(0).choice(len(halves), size=rows, replace=False))
+        halves = halves[index]
+        np.save(os.path.join(directory, "proof_words_index.npy"), index.astype(np.float64))
+    np.save(os.path.join(directory, "proof_words.npy"), halves)
+
+
 def smi_snapshot():
     """clocks / power of the GPU as rocm-smi reports them (diagnostics for a run that lands on a slow box)"""
     import subprocess
@@ -652,7 +681,14 @@ def main():
                     help="host side that sequences the C-ABI calls of the timed step: the C++ mirror of Prover::prove "
                          "(triton_vm_amd/host/, the default where it applies: cached tables, one proof per GPU) or the "
                          "Python mirror (always used for --jit-passes and the sharded proof)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline: verify the last proof, profile the stages, time the roofline kernels, and (single GPU) run the "
+                         "extras and the CPU baseline.  Without it a run sets up, warms up, times the steps and prints the headline line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned -- the proof words -- to DIR/proof_words.npy (see dump_outputs)")
     args = ap.parse_args()
+    if args.simulate_gpus and not args.full:
+        ap.error("--simulate-gpus is a measurement beside the headline: run it with --full")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` without a launcher: start the N ranks ourselves (one process per GPU, the same
@@ -784,9 +820,14 @@ def main():
         elif host_lib is not None:
             native = native_host.NativeProver(ctx, host_lib, params, prover.main.d_trace, prover.main.d_randomizers,
                                               prover.aux.d_trace, prover.aux.d_randomizers, prover.quotient_randomizer)
-            step, host = (lambda: native.prove(parse=False)), "cpp"
+            step, host = (lambda: native.prove(parse=bool(args.dump_outputs))), "cpp"
+        timed_step = step
+        step = lambda: last.__setitem__("result", timed_step())   # noqa: E731  (what the step hands back, for --dump-outputs)
 
     elapsed = timed_steps(step, args.steps, args.warmup, ctx.sync, dist, device=dev_kind)
+    if args.dump_outputs and rank == 0:
+        result = last["proof"] if args.data == "real" else last["result"]
+        dump_outputs(args.dump_outputs, result.proof().words if hasattr(result, "proof") else result)
 
     def barrier():
         ctx.sync()
@@ -795,7 +836,7 @@ def main():
 
     # ---- after the timed region: acceptance of the last proof, the per-stage profile, the roofline kernels, the extras -------
     verified = None
-    if args.data == "real" and rank == 0:
+    if args.full and args.data == "real" and rank == 0:
         from triton_vm_amd.verifier import Verifier
 
         t0 = time.perf_counter()
@@ -804,7 +845,7 @@ def main():
                     "revealed_rows": len(accepted_at), "proof_words": int(last["proof"].size), "seconds": round(time.perf_counter() - t0, 2)}
     barrier()
     stage_ms, stage_wall, t_prof, rank_stats = {}, {}, 0.0, None
-    cpp_stats = host_lib is not None and (sharded or coset_wise) and args.data == "real"
+    cpp_stats = args.full and host_lib is not None and (sharded or coset_wise) and args.data == "real"
     if cpp_stats:   # the sharded / coset-wise C++ host times its own stages (stream drained at every stage boundary)
         t_prof = time.perf_counter()
         prove_from(resident, profile=True)
@@ -814,7 +855,7 @@ def main():
             rank_stats = [None] * world
             dist.all_gather_object(rank_stats, last["stats"])
         stage_ms = dict(rank_stats[0]["stage_ms"])
-    elif (rank == 0 or sharded) and not (host_lib is not None and (sharded or coset_wise)):  # a sharded prove() contains collectives: every rank has to take part
+    elif args.full and (rank == 0 or sharded) and not (host_lib is not None and (sharded or coset_wise)):  # a sharded prove() contains collectives: every rank has to take part
         if args.data == "real":
             if sharded:
                 from triton_vm_amd.sharded import ShardedProver
@@ -837,7 +878,7 @@ def main():
     # own stage times of one more proof, through its sharded entry with no communicator and one pass (the same kernels in the same
     # order; the stream drained at every stage boundary): what the C++ host spends per stage.
     stage_ms_cpp = None
-    if rank == 0 and world == 1 and host_lib is not None and args.data == "real" and not cpp_stats:
+    if args.full and rank == 0 and world == 1 and host_lib is not None and args.data == "real" and not cpp_stats:
         try:
             _, st = native_host.prove_execution_sharded(ctx, host_lib, None, resident, padded_height, claim, PROVER_SEED, jit_passes=1,
                                                         profile=True, **kw)   # first call: allocations
@@ -847,8 +888,9 @@ def main():
         except Exception as e:  # noqa: BLE001  (reported, never fatal for the line)
             stage_ms_cpp = {"error": str(e)[:200]}
     lde_avg_ms = hash_avg_ms = None
-    if rank == 0:
-        passes_used = int((rank_stats or [{}])[0].get("passes", 0) or 0) if not sharded else 0   # what the memory policy settled on
+    # what the memory policy settled on: the profiled proof's or, without --full, the last timed proof's
+    passes_used = int((rank_stats or [last.get("stats") or {}])[0].get("passes", 0) or 0) if not sharded else 0
+    if args.full and rank == 0:
         share = world if sharded else (passes_used or args.jit_passes or 1)
         kp = params
         if share > 1:   # a rank (or a coset-wise pass) extends onto its share of the rows
@@ -862,15 +904,6 @@ def main():
     if rank == 0:
         ms_per_step = 1e3 * elapsed / args.steps
         share = world if sharded else (passes_used or args.jit_passes or 1)
-        counters = kernel_counters()
-        expansion = params.ldt.length // params.trace.length
-        shape_key = f"2p{args.log2_rows}_x{expansion}"
-        if counters and share == 1 and shape_key in counters.get("shapes", {}):   # counters taken on this shape (tools/kernel_counters.py)
-            counters = counters["shapes"][shape_key]
-            shape_ok = True
-        else:
-            shape_ok = share == 1 and args.log2_expansion == 2 and args.log2_rows == 20   # (the default counters were taken on this shape)
-        roofline = lde_roofline(lde_avg_ms, params.trace.length, 379, expansion, share, counters, shape_ok)
         if args.data == "real":
             workload_text = (f"Prover::prove(claim, aet) for real: {args.program} program run for {e['cycles']} cycles (public input "
                              f"{e['index']}), padded height 2^{args.log2_rows}, 379 main + 91 aux columns (652 words/row); Stark::default() parameters with "
@@ -905,13 +938,24 @@ def main():
                                        else f"single GPU, tables evaluated coset-wise in {share} passes (nothing cached)"
                                        + (" -- chosen by the host's memory policy (jit_passes = 0: the cached path first)" if args.memory_policy and not args.jit_passes else "")
                                        if coset_wise and share > 1 else "single GPU")},
-            "roofline": roofline,
-            "roofline_valu": hash_roofline(hash_avg_ms, hash_rows, 379, counters),
-            "stage_ms": {k: round(v, 3) for k, v in stage_ms.items()},
-            "stage_wall_ms": {k: round(v, 3) for k, v in stage_wall.items()},
-            **({"stage_ms_cpp_host": stage_ms_cpp} if stage_ms_cpp is not None else {}),
-            "profiled_prove_wall_ms": round(t_prof, 3),
         }
+        if args.full:
+            counters = kernel_counters()
+            expansion = params.ldt.length // params.trace.length
+            shape_key = f"2p{args.log2_rows}_x{expansion}"
+            if counters and share == 1 and shape_key in counters.get("shapes", {}):   # counters taken on this shape (tools/kernel_counters.py)
+                counters = counters["shapes"][shape_key]
+                shape_ok = True
+            else:
+                shape_ok = share == 1 and args.log2_expansion == 2 and args.log2_rows == 20   # (the default counters were taken on this shape)
+            out.update({
+                "roofline": lde_roofline(lde_avg_ms, params.trace.length, 379, expansion, share, counters, shape_ok),
+                "roofline_valu": hash_roofline(hash_avg_ms, hash_rows, 379, counters),
+                "stage_ms": {k: round(v, 3) for k, v in stage_ms.items()},
+                "stage_wall_ms": {k: round(v, 3) for k, v in stage_wall.items()},
+                **({"stage_ms_cpp_host": stage_ms_cpp} if stage_ms_cpp is not None else {}),
+                "profiled_prove_wall_ms": round(t_prof, 3),
+            })
         if verified is not None:
             out["verified"] = verified
         if args.memory_policy and not sharded:
@@ -926,7 +970,7 @@ def main():
         if stage_ms.get("AIR quotients", 0.0) > (80.0 if args.log2_rows == 20 and world == 1 else 1e9):
             # the unexplained slow mode of the AIR kernels seen on 2 of ~40 boxes in round 2 (HISTORY.md 5.1): leave evidence
             out["air_slow_mode"] = {"stage_ms": stage_ms["AIR quotients"], "smi": smi_snapshot()}
-        extras = world == 1 and not sharded and not coset_wise and not args.no_extras
+        extras = args.full and world == 1 and not sharded and not coset_wise and not args.no_extras
         if extras and args.data == "real":
             # (1) the same step with the execution trace in host memory (what a host that keeps the AET in RAM pays)
             t = timed_steps(lambda: prove_from(e["aet"]), 3, 1, ctx.sync)
@@ -986,7 +1030,7 @@ def main():
             ctx.assume_valid_trace(False)
             out["valid_trace_mode"] = {"option": "TVM_OPTION_AIR_VALID_TRACE", "ms_per_step": round(1e3 * t / 3, 3),
                                        "value": round(cells_per_step * 3 / t, 1), "unit": "trace-cells/s"}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = (cpu_baseline_full if args.cpu_baseline == "full" else cpu_baseline)(args.log2_rows, args.log2_expansion)
             if args.cpu_baseline != "full":
                 out["cpu_baseline"]["full_run_on_record"] = cpu_baseline_full_on_record(args.log2_rows)

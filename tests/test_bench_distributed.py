@@ -76,7 +76,7 @@ def test_bench_script_runs_under_torchrun_with_two_ranks(mode):
     env = dict(os.environ, OMP_NUM_THREADS="1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(ROOT, "tests", "bench_on_emulation.py"), "--gpus", "2", "--steps", "1", "--warmup", "0",
-           "--data", "synthetic", "--log2-rows", "3", "--trace-randomizers", "3", "--queries", "2", "--no-cpu-baseline"] + (["--replicas"] if mode == "replicas" else [])
+           "--data", "synthetic", "--log2-rows", "3", "--trace-randomizers", "3", "--queries", "2", "--no-cpu-baseline", "--full"] + (["--replicas"] if mode == "replicas" else [])
     out = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
@@ -118,7 +118,7 @@ def test_bench_sharded_code_path_over_rccl_with_one_rank():
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--sharded", "--split-all-trees", "--steps", "1", "--warmup", "0", "--log2-rows", "16",
-           "--no-cpu-baseline", "--no-extras"]
+           "--no-cpu-baseline", "--no-extras", "--full"]
     out = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-2000:]
     rec = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("{")][-1])
@@ -140,7 +140,7 @@ def test_bench_lockstep_measurement_of_the_multi_gpu_code_path():
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--simulate-gpus", "4", "--steps", "1", "--warmup", "0", "--log2-rows", "16",
-           "--no-cpu-baseline", "--no-extras"]
+           "--no-cpu-baseline", "--no-extras", "--full"]
     out = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-2000:]
     rec = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("{")][-1])
@@ -160,7 +160,7 @@ def test_bench_memory_policy():
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     cmd = [sys.executable, os.path.join(ROOT, "tests", "bench_on_emulation.py"), "--steps", "1", "--warmup", "0", "--log2-rows", "9",
-           "--no-cpu-baseline", "--no-extras", "--memory-policy"]
+           "--no-cpu-baseline", "--no-extras", "--memory-policy", "--full"]
     out = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=1800)
     assert out.returncode == 0, out.stderr[-2000:]
     rec = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("{")][-1])
