@@ -85,6 +85,12 @@ int32_t tvm_ctx_trim(tvm_ctx* ctx);
 /* TVM_OPTION_MERKLE_SUBTREES (default 1): the levels of a Merkle tree between 32768 and 64 parents are built up to seven to a launch
  * (a workgroup per subtree of 64 parents); 0: one launch per level (A/B). */
 #define TVM_OPTION_MERKLE_SUBTREES 6
+/* TVM_OPTION_AIR_REMAINDER_COSET (default 1): in valid-trace mode, tvm_all_quotients_combined evaluates each class of constraints on one
+ * coset of the trace domain fewer than its quotient has blocks of trace-length coefficients, plus one block of rows of another coset
+ * (the remainder set) that pays for the few coefficients beyond them; 0: the whole cosets (A/B).  The same words either way.
+ * TVM_OPTION_AIR_REMAINDER_MIN_ROWS: the shortest trace domain this applies to (default 2^18; 0 restores it) -- the tests lower it. */
+#define TVM_OPTION_AIR_REMAINDER_COSET 7
+#define TVM_OPTION_AIR_REMAINDER_MIN_ROWS 8
 int32_t tvm_ctx_set_option(tvm_ctx* ctx, int32_t option, uint64_t value);
 /* Cap on the bytes this context may hold through tvm_malloc / table handles (0 = no cap).  Requests beyond it fail
  * with TVM_ERR_OUT_OF_MEMORY exactly like a full device: the knob a host uses to share a GPU, and what the tests use to

@@ -264,6 +264,12 @@ class Context:
         four streams side by side, and valid-trace mode evaluates them row by row (0: never; the library's default is 256)"""
         self._check(self.lib.tvm_ctx_set_option(self.handle, 5, n), "tvm_ctx_set_option")
 
+    def air_remainder_coset(self, on=True, min_rows=0):
+        """TVM_OPTION_AIR_REMAINDER_COSET / _MIN_ROWS: valid-trace mode evaluates each class of constraints on one coset fewer plus
+        one block of rows of another coset, on trace domains of at least min_rows rows (0: the library's default, 2^18)"""
+        self._check(self.lib.tvm_ctx_set_option(self.handle, 7, 1 if on else 0), "tvm_ctx_set_option")
+        self._check(self.lib.tvm_ctx_set_option(self.handle, 8, min_rows), "tvm_ctx_set_option")
+
     def trim(self):
         """give the cached device blocks back to the driver"""
         self._check(self.lib.tvm_ctx_trim(self.handle), "tvm_ctx_trim")

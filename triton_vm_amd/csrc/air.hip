@@ -176,6 +176,9 @@ bool fork_lanes(tvm_ctx* c) {
     return true;
 }
 
+static int air_run(tvm_ctx* c, AirArgs a, u64 trace_len, u64 trace_gen, u64 q_offset, u64 q_gen, u64 index_step,
+                   const u64* d_challenges, const u64* d_weights, u64* d_out, int part_select, int accumulate);
+
 int all_quotients_combined(tvm_ctx* c, const u64* main_table, const TabLayout& layout, u64 main_w, const u64* aux_table,
                            u64 aux_w, u64 trace_len, u64 trace_gen, u64 q_offset, u64 q_gen, u64 q_len,
                            const u64* d_challenges, const u64* d_weights, u64* d_out, int part_select, int accumulate) {
@@ -207,6 +210,39 @@ int all_quotients_combined(tvm_ctx* c, const u64* main_table, const TabLayout& l
     const u64 reach = a.tiled ? (WPB + 1) * layout.n1 + TVM_RB : layout.storage_rows() + layout.n1 + TVM_RB;  // rows a 32-bit lane offset must span
     if (reach * wider * 8 >= (1ull << 32))
         return set_error(c, TVM_ERR_UNSUPPORTED, "quotients: table shape beyond the 32-bit lane offsets of the AIR kernels");
+    // (domain-index distance of rows j2, j2 + 1 of a block: X' * n2)
+    return air_run(c, a, trace_len, trace_gen, q_offset, q_gen, (q_len / trace_len) << layout.log_n2, d_challenges, d_weights, d_out,
+                   part_select, accumulate);
+}
+
+int air_quotients_on_block(tvm_ctx* c, const u64* main_block, u64 main_w, const u64* aux_block, u64 aux_w, u64 n1, u64 trace_len,
+                           u64 trace_gen, u64 offset, u64 gen, const u64* d_challenges, const u64* d_weights, u64* d_out, int part_select) {
+    if (!is_pow2(n1) || !is_pow2(trace_len) || n1 > trace_len || n1 % TVM_RB)
+        return set_error(c, TVM_ERR_INVALID_ARGUMENT, "quotients on a block: lengths");
+    // one "coset" of n1 rows in a single block: work item t is storage row t, its successor t + n1, its domain index t
+    AirArgs a;
+    a.main_table = main_block;
+    a.aux_table = aux_block;
+    a.main_w = main_w;
+    a.aux_w = aux_w;
+    a.q_len = n1;
+    a.n1 = n1;
+    a.log_n1 = a.log_n = ilog2(n1);
+    a.log_n2 = 0;
+    a.log_xq = 0;
+    a.coset_rows = 0;
+    a.tiled = 0;
+    const u64 wider = main_w > aux_w ? main_w : aux_w;
+    if ((2 * n1 + TVM_RB) * wider * 8 >= (1ull << 32))
+        return set_error(c, TVM_ERR_UNSUPPORTED, "quotients on a block: beyond the 32-bit lane offsets of the AIR kernels");
+    return air_run(c, a, trace_len, trace_gen, offset, gen, 1, d_challenges, d_weights, d_out, part_select, 0);
+}
+
+// the parts selected by part_select on the rows a describes (its table pointers, shape and q_len set), the zerofier inverses of
+// the points q_offset * q_gen^index, and their scatter into d_out
+static int air_run(tvm_ctx* c, AirArgs a, u64 trace_len, u64 trace_gen, u64 q_offset, u64 q_gen, u64 index_step,
+                   const u64* d_challenges, const u64* d_weights, u64* d_out, int part_select, int accumulate) {
+    const u64 q_len = a.q_len;
     // Fork: a part on a short quotient domain is a few workgroups that run for the latency of its ~1000 dependent multiplications
     // (80-130 us) whatever their number; ten of them one behind the other are a millisecond of a proof that takes eight.  While one
     // part leaves most of the chip empty (grid <= air_fork_max_workgroups) the selected parts go out on the context's stream and its
@@ -232,7 +268,7 @@ int all_quotients_combined(tvm_ctx* c, const u64* main_table, const TabLayout& l
         z.q_gen = q_gen;
         z.trace_len = trace_len;
         z.trace_gen_inv = bfe_inv(trace_gen);
-        z.index_step = (q_len / trace_len) << layout.log_n2;
+        z.index_step = index_step;
         z.x_step = bfe_pow(q_gen, z.index_step);
         z.zinv = zinv;
         const u64 n_threads = (q_len + AIR_ZB - 1) / AIR_ZB;
@@ -278,7 +314,7 @@ int all_quotients_combined(tvm_ctx* c, const u64* main_table, const TabLayout& l
             return set_error(c, fe == hipErrorOutOfMemory ? TVM_ERR_OUT_OF_MEMORY : TVM_ERR_DEVICE, "quotients: fork lanes");
         }
     }
-    const u64 cosets = q_len / trace_len;
+    const u64 cosets = 1ull << a.log_xq;
     if (a.tiled && (1ull << a.log_n2) >= AIR_SCATTER_PAIRS / (cosets < 8 ? cosets : 8))
         TVM_LAUNCH(k_air_scatter_tiles, dim3((unsigned)(q_len / (16 * AIR_SCATTER_PAIRS))), dim3(256), 0, c->stream, a, (const u64*)acc,
                    n_lanes, d_out, accumulate);

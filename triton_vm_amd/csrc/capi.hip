@@ -144,6 +144,14 @@ int32_t tvm_ctx_set_option(tvm_ctx* c, int32_t option, uint64_t value) {
         c->air_fork_max_workgroups = value;
         return TVM_OK;
     }
+    if (option == TVM_OPTION_AIR_REMAINDER_COSET) {
+        c->air_remainder_coset = value != 0;
+        return TVM_OK;
+    }
+    if (option == TVM_OPTION_AIR_REMAINDER_MIN_ROWS) {
+        c->air_remainder_min_rows = value ? value : 1ull << 18;
+        return TVM_OK;
+    }
     if (option == TVM_OPTION_MERKLE_MIN_WORKGROUPS) {
         c->merkle_min_workgroups = value ? value : 4096;
         return TVM_OK;
@@ -648,6 +656,70 @@ __global__ void k_coset_combine(CosetCombinePointers p, int n, u64 N, CosetCombi
         o[0] = acc.c0, o[1] = acc.c1, o[2] = acc.c2;
     }
 }
+// The inverse of the n x n Vandermonde matrix of cs[0 .. n-1] (n <= 4) into w (w[4 i + j], zero elsewhere): row i holds the coefficients
+// of x^i in the Lagrange basis polynomials L_j(x) = prod_{l != j} (x - c_l) / (c_j - c_l).  false if two of the c_j are equal.
+static bool coset_combine_weights(const u64* cs, uint32_t n, CosetCombineWeights& w) {
+    for (int i = 0; i < 16; i++) w.w[i] = 0;
+    for (uint32_t j = 0; j < n; j++) {
+        u64 poly[4] = {TVM_ONE, 0, 0, 0};   // running product prod (x - c_l), low coefficient first
+        u64 denom = TVM_ONE;
+        int deg = 0;
+        for (uint32_t l = 0; l < n; l++) {
+            if (l == j) continue;
+            if (cs[l] == cs[j]) return false;
+            for (int e = deg + 1; e >= 1; e--) poly[e] = bfe_sub(poly[e - 1], bfe_mul(poly[e], cs[l]));
+            poly[0] = bfe_neg(bfe_mul(poly[0], cs[l]));
+            deg++;
+            denom = bfe_mul(denom, bfe_sub(cs[j], cs[l]));
+        }
+        const u64 dinv = bfe_inv(denom);
+        for (uint32_t i = 0; i < n; i++) w.w[4 * i + j] = bfe_mul(poly[i], dinv);
+    }
+    return true;
+}
+// The remainder set (tvm_all_quotients_combined, valid-trace mode): partial[g][i] = sum_{r < R} d^(gR + r) sum_j lambda_j q_j[i + (gR + r) M]
+// for g < G, i < M -- the polynomial sum_j lambda_j q_j of G R M coefficients modulo X^M - d, as G partial sums (k_remainder_scatter
+// adds them up)
+struct RemainderFold {
+    const u64* q[4];
+    u64 lambda[4];
+    int n;
+};
+__global__ void k_remainder_fold(RemainderFold f, u64 M, u64 G, u64 R, u64 d, u64* __restrict__ partial) {
+    const u64 e = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= G * M) return;
+    const u64 i = e % M, g = e / M;
+    u64 s = bfe_pow(d, g * R);
+    xfe acc = xfe_zero();
+    for (u64 r = 0; r < R; r++) {
+        const u64 row = 3 * (i + (g * R + r) * M);
+        xfe v = xfe_zero();
+        for (int j = 0; j < f.n; j++) v = xfe_add(v, xfe_mul_bfe(xfe_make(f.q[j][row], f.q[j][row + 1], f.q[j][row + 2]), f.lambda[j]));
+        acc = xfe_add(acc, xfe_mul_bfe(v, s));
+        s = bfe_mul(s, d);
+    }
+    partial[3 * e] = acc.c0, partial[3 * e + 1] = acc.c1, partial[3 * e + 2] = acc.c2;
+}
+// b = p[i] - sum_g partial[g][i] (the interpolant of q - R on the remainder set, i < M);  coeffs[i + k N] += v[k] * b, k < n_v
+struct RemainderScatter {
+    u64 v[4];
+    int n_v;
+};
+__global__ void k_remainder_scatter(const u64* __restrict__ p, const u64* __restrict__ partial, u64 G, u64 M, u64 N, RemainderScatter w,
+                                    u64* __restrict__ coeffs) {
+    const u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= M) return;
+    xfe b = xfe_make(p[3 * i], p[3 * i + 1], p[3 * i + 2]);
+    for (u64 g = 0; g < G; g++) {
+        const u64* x = partial + 3 * (g * M + i);
+        b = xfe_sub(b, xfe_make(x[0], x[1], x[2]));
+    }
+    for (int k = 0; k < w.n_v; k++) {
+        u64* o = coeffs + 3 * (i + (u64)k * N);
+        const xfe r = xfe_add(xfe_make(o[0], o[1], o[2]), xfe_mul_bfe(b, w.v[k]));
+        o[0] = r.c0, o[1] = r.c1, o[2] = r.c2;
+    }
+}
 __global__ void k_three_coset_combine(const u64* __restrict__ q0, const u64* __restrict__ q1, const u64* __restrict__ q2, u64 n,
                                       ThreeCosetWeights m, u64* __restrict__ coeffs) {
     const u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
@@ -941,6 +1013,97 @@ int32_t tvm_extend_aux_table(tvm_ctx* c, const uint64_t* d_main_trace, uint64_t*
     return extend_aux_table(c, d_main_trace, d_aux_trace, staged, n_rows);
 }
 
+// Valid-trace mode, one coset fewer per class (tvm_all_quotients_combined below).  A class's quotient q has fewer than nN + s coefficients,
+// s <= M = n1 (the rows of one block of the tables).  With S the n cosets gamma_k <w_N> (X^N = c_k there) and V(X) = prod_{k in S} (X^N - c_k),
+//   q = R + V B,  deg R < nN,  deg B < s:
+// R is the interpolant of q's values on S -- n N-point interpolations Q_k, combined by the inverse Vandermonde matrix of the c_k
+// (k_coset_combine, as tvm_coset_values_to_coefficients).  B comes from q on ONE BLOCK T of another coset: its n1 storage rows are the
+// points tau w_M^i, i < M (tau = gamma_T w_N^0, w_M = w_N^n2, a coset of the order-M subgroup) and their successors are the next block
+// (context.h), so the AIR evaluates them like a coset of their own (air_quotients_on_block).  On T, X^N is the constant c'' = gamma_T^N
+// and V the constant beta = prod (c'' - c_k); R restricted to gamma_T <w_N> is sum_k L_k(c'') Q_k (L_k the Lagrange basis in the c_k),
+// which modulo X^M - tau^M is the interpolant of R on T (k_remainder_fold).  So B = (interpolant of q on T - that fold) / beta, and V B
+// adds v_i / beta times it at the coefficients i N + (0 .. M-1) (k_remainder_scatter).  On a valid trace B's coefficients s .. M-1 are zero.
+namespace tvm {
+static int quotients_by_remainder_coset(tvm_ctx* c, const tvm_table* mt, const tvm_table* at, tvm_domain td, tvm_domain qd, const u64* d_ch,
+                                        const u64* d_w, u64* d_out) {
+    const u64 N = td.length, M = mt->layout.n1, n2 = mt->layout.n2, pitch = mt->layout.pitch, X = qd.length / N;
+    const u64 G = n2 < 64 ? n2 : 64, R = n2 / G;   // the fold: G partial sums of R chunks of M coefficients
+    PoolBlock block(c, (size_t)3 * (4 * N + N + 3 * N + 2 * M + G * M) * sizeof(u64));   // released on every exit path
+    u64* coeffs = (u64*)block.p;   // [4N] XFE: the sum of the classes' quotients
+    if (!coeffs) return set_error(c, TVM_ERR_OUT_OF_MEMORY, "quotient scratch");
+    u64* vals = coeffs + 12 * N;   // [N] XFE: a class on one coset
+    u64* q = vals + 3 * N;         // [3][N] XFE: its interpolants Q_k
+    u64* q_t = q + 9 * N;          // [M] XFE: a class on T, then ...
+    u64* p_t = q_t + 3 * M;        // ... its interpolant there
+    u64* partial = p_t + 3 * M;    // [G][M] XFE
+    TVM_HIP_CHECK(c, hipMemsetAsync(coeffs, 0, (size_t)12 * N * sizeof(u64), c->stream));
+    const u64 g_n = bfe_pow(qd.generator, X), g_m = bfe_pow(g_n, n2);
+    // (the cosets of the tables ARE those of the quotient domain here: the gate asks for X == layout.X)
+    const u64 k_t = 6, gamma_t = bfe_mul(qd.offset, bfe_pow(qd.generator, k_t)), c_t = bfe_pow(gamma_t, N), d_t = bfe_pow(gamma_t, M);
+    const u64* main_t = mt->data + tvm_tab_idx(k_t * pitch, 0, (u64)mt->W);
+    const u64* aux_t = at->data + tvm_tab_idx(k_t * pitch, 0, (u64)at->W);
+    TabLayout lm = mt->layout;   // one coset of the tables: a table of its own
+    lm.X = 1;
+    lm.log_x = 0;
+    const int CLASS_HALF = 1 << 1, CLASS_QUARTER = 1 << 2, CLASS_THREE = 1 << 3;
+    struct {
+        int mask;
+        uint32_t n;
+    } const classes[3] = {{CLASS_HALF, 3}, {CLASS_THREE, 2}, {CLASS_QUARTER, 1}};   // S = cosets 0, 2, 4 (the first n of them)
+    for (const auto& cl : classes) {
+        u64 cs[3];
+        CosetCombinePointers ptrs;
+        for (uint32_t j = 0; j < 4; j++) ptrs.q[j] = nullptr;
+        for (uint32_t j = 0; j < cl.n; j++) {
+            const u64 k = 2 * (u64)j;
+            const tvm_domain dom = {bfe_mul(qd.offset, bfe_pow(qd.generator, k)), g_n, N};
+            cs[j] = bfe_pow(dom.offset, N);
+            TVM_TRY(all_quotients_combined(c, mt->data + tvm_tab_idx(k * pitch, 0, (u64)mt->W), lm, (u64)mt->W,
+                                           at->data + tvm_tab_idx(k * pitch, 0, (u64)at->W), (u64)at->W, N, td.generator, dom.offset,
+                                           dom.generator, N, d_ch, d_w, vals, cl.mask, 0));
+            TVM_TRY(tvm_interpolate(c, 3, vals, dom, q + 3 * N * j));
+            ptrs.q[j] = q + 3 * N * j;
+        }
+        CosetCombineWeights w;
+        if (!coset_combine_weights(cs, cl.n, w)) return set_error(c, TVM_ERR_INVALID_ARGUMENT, "quotients: two cosets with the same X^N");
+        TVM_LAUNCH(k_coset_combine, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, c->stream, ptrs, (int)cl.n, N, w, coeffs);   // += R
+        // R on T, modulo X^M - tau^M: the Lagrange weights L_j(c'') = sum_i c''^i w[4 i + j]
+        RemainderFold f;
+        f.n = (int)cl.n;
+        for (uint32_t j = 0; j < 4; j++) {
+            f.q[j] = ptrs.q[j];
+            f.lambda[j] = 0;
+        }
+        for (uint32_t j = 0; j < cl.n; j++) {
+            u64 ci = TVM_ONE;
+            for (uint32_t i = 0; i < cl.n; i++, ci = bfe_mul(ci, c_t)) f.lambda[j] = bfe_add(f.lambda[j], bfe_mul(ci, w.w[4 * i + j]));
+        }
+        TVM_LAUNCH(k_remainder_fold, dim3((unsigned)((G * M + 255) / 256)), dim3(256), 0, c->stream, f, M, G, R, d_t, partial);
+        // q on T, its interpolant there
+        TVM_TRY(air_quotients_on_block(c, main_t, (u64)mt->W, aux_t, (u64)at->W, M, N, td.generator, gamma_t, g_m, d_ch, d_w, q_t, cl.mask));
+        TVM_TRY(tvm_interpolate(c, 3, q_t, tvm_domain{gamma_t, g_m, M}, p_t));
+        // V = prod (Y - c_k) in Y = X^N, its coefficients divided by beta = V(c'')
+        RemainderScatter v;
+        v.n_v = (int)cl.n + 1;
+        u64 beta = TVM_ONE;
+        for (int i = 0; i < 4; i++) v.v[i] = 0;
+        v.v[0] = TVM_ONE;
+        for (uint32_t j = 0; j < cl.n; j++) {
+            for (int e = (int)j + 1; e >= 1; e--) v.v[e] = bfe_sub(v.v[e - 1], bfe_mul(v.v[e], cs[j]));
+            v.v[0] = bfe_neg(bfe_mul(v.v[0], cs[j]));
+            beta = bfe_mul(beta, bfe_sub(c_t, cs[j]));
+        }
+        const u64 beta_inv = bfe_inv(beta);
+        for (int i = 0; i < v.n_v; i++) v.v[i] = bfe_mul(v.v[i], beta_inv);
+        TVM_LAUNCH(k_remainder_scatter, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, c->stream, p_t, partial, G, M, N, v, coeffs);
+        TVM_HIP_CHECK(c, hipGetLastError());
+    }
+    TVM_TRY(tvm_evaluate(c, 3, coeffs, 4 * N, qd, d_out));
+    return all_quotients_combined(c, mt->data, mt->layout, (u64)mt->W, at->data, (u64)at->W, N, td.generator, qd.offset, qd.generator,
+                                  qd.length, d_ch, d_w, d_out, 1 << 0, 1);
+}
+}  // namespace tvm
+
 int32_t tvm_all_quotients_combined(tvm_ctx* c, const tvm_table* mt, const tvm_table* at, tvm_domain td,
                                               tvm_domain qd, const uint64_t* h_challenges, const uint64_t* h_weights,
                                               uint64_t* d_out) {
@@ -984,6 +1147,16 @@ int32_t tvm_all_quotients_combined(tvm_ctx* c, const tvm_table* mt, const tvm_ta
     const bool split4 = quarter >= 2 * N && quarter % N == 0 && 2 * (m - 1) + 2 <= quarter + N && m <= quarter;
     const bool split3 = split4 && half == 4 * N && 3 * (m - 1) + 2 <= 4 * N && 2 * (m - 1) <= 3 * N && mt->layout.X == at->layout.X &&
                         mt->layout.pitch == at->layout.pitch && mt->layout.X == 2 * (half / N) && mt->layout.pitch % TVM_RB == 0;
+    // One coset fewer per class, plus one block T of a sixth coset (quotients_by_remainder_coset, above): when every class's quotient
+    // has at most M = n1 coefficients beyond its whole blocks of N -- class 1 (parts 1-5) fewer than 3N + 4h, class 3 (6, 7) 2N + 3h,
+    // class 2 (8, 9) N + 2h -- and the trace is long enough that the dropped cosets (about 1.9 ms of AIR work at 2^18 rows, a quarter of
+    // that at 2^16) outweigh the latency of the three short evaluations on T (about 0.1 ms each, whatever N).
+    const u64 M = mt->layout.n1;
+    if (split3 && c->air_remainder_coset && N >= c->air_remainder_min_rows && M % TVM_RB == 0 &&
+        4 * (m - 1) + 2 <= 4 * N + M && 3 * (m - 1) <= 3 * N + M &&     // class 1
+        3 * (m - 1) + 2 <= 3 * N + M && 2 * (m - 1) <= 2 * N + M &&     // class 3
+        2 * (m - 1) + 2 <= 2 * N + M && m <= N + M)                     // class 2
+        return tvm::quotients_by_remainder_coset(c, mt, at, td, qd, d_ch, d_w, d_out);
     PoolBlock low_block(c, (size_t)(2 * 3 * half + (split4 ? 2 * 3 * quarter : 0) + (split3 ? 6 * 3 * N : 0)) * sizeof(u64));  // released on every exit path
     u64* low = (u64*)low_block.p;
     if (!low) return set_error(c, TVM_ERR_OUT_OF_MEMORY, "quotient scratch");
@@ -1114,22 +1287,8 @@ int32_t tvm_coset_values_to_coefficients(tvm_ctx* c, tvm_domain td, uint32_t n_c
     u64 cs[4];
     for (uint32_t j = 0; j < n_cosets; j++) cs[j] = bfe_pow(h_offsets[j], N);
     tvm::CosetCombineWeights w;
-    for (int i = 0; i < 16; i++) w.w[i] = 0;
-    for (uint32_t j = 0; j < n_cosets; j++) {
-        u64 poly[4] = {TVM_ONE, 0, 0, 0};   // running product prod (x - c_l), low coefficient first
-        u64 denom = TVM_ONE;
-        int deg = 0;
-        for (uint32_t l = 0; l < n_cosets; l++) {
-            if (l == j) continue;
-            if (cs[l] == cs[j]) return set_error(c, TVM_ERR_INVALID_ARGUMENT, "coset_values_to_coefficients: two cosets with the same X^N");
-            for (int e = deg + 1; e >= 1; e--) poly[e] = bfe_sub(poly[e - 1], bfe_mul(poly[e], cs[l]));
-            poly[0] = bfe_neg(bfe_mul(poly[0], cs[l]));
-            deg++;
-            denom = bfe_mul(denom, bfe_sub(cs[j], cs[l]));
-        }
-        const u64 dinv = bfe_inv(denom);
-        for (uint32_t i = 0; i < n_cosets; i++) w.w[4 * i + j] = bfe_mul(poly[i], dinv);
-    }
+    if (!tvm::coset_combine_weights(cs, n_cosets, w))
+        return set_error(c, TVM_ERR_INVALID_ARGUMENT, "coset_values_to_coefficients: two cosets with the same X^N");
     PoolBlock block(c, (size_t)n_cosets * 3 * N * sizeof(u64));
     u64* q = (u64*)block.p;
     if (!q) return set_error(c, TVM_ERR_OUT_OF_MEMORY, "coset interpolants");

@@ -61,6 +61,11 @@ int verifier_deep_values(tvm_ctx* c, const u64* d_main_rows, int n_main, const u
 int all_quotients_combined(tvm_ctx* c, const u64* main_table, const TabLayout& layout, u64 main_w, const u64* aux_table,
                            u64 aux_w, u64 trace_len, u64 trace_gen, u64 q_offset, u64 q_gen, u64 q_len, const u64* d_challenges,
                            const u64* d_weights, u64* d_out, int part_select = 0, int accumulate = 0);
+// The same on ONE block of a table made by tvm_lde_table: the n1 consecutive storage rows that start at main_block / aux_block, whose
+// successor rows are the next n1 (context.h) -- the points offset * gen^i, i < n1, a coset of the order-n1 subgroup.  Out: n1 XFE in
+// that order.
+int air_quotients_on_block(tvm_ctx* c, const u64* main_block, u64 main_w, const u64* aux_block, u64 aux_w, u64 n1, u64 trace_len,
+                           u64 trace_gen, u64 offset, u64 gen, const u64* d_challenges, const u64* d_weights, u64* d_out, int part_select);
 // a quotient domain this short leaves the chip to the parts side by side (the fork lanes): the row-by-row evaluation of all ten
 // parts then costs what its longest lane does, less than valid-trace mode's six evaluations and five transforms one behind another
 bool air_parts_fork(const tvm_ctx* c, u64 q_len);
