@@ -91,6 +91,9 @@ int32_t tvm_ctx_trim(tvm_ctx* ctx);
  * TVM_OPTION_AIR_REMAINDER_MIN_ROWS: the shortest trace domain this applies to (default 2^18; 0 restores it) -- the tests lower it. */
 #define TVM_OPTION_AIR_REMAINDER_COSET 7
 #define TVM_OPTION_AIR_REMAINDER_MIN_ROWS 8
+/* TVM_OPTION_AIR_CHECK_CHUNK_ROWS: rows per chunk of tvm_check_constraints (a power of two in 16 .. 2^20; default 2^18, 0 restores it)
+ * -- the tests lower it to reach the chunk boundaries with small traces.  The same report for every value. */
+#define TVM_OPTION_AIR_CHECK_CHUNK_ROWS 9
 int32_t tvm_ctx_set_option(tvm_ctx* ctx, int32_t option, uint64_t value);
 /* Cap on the bytes this context may hold through tvm_malloc / table handles (0 = no cap).  Requests beyond it fail
  * with TVM_ERR_OUT_OF_MEMORY exactly like a full device: the knob a host uses to share a GPU, and what the tests use to
@@ -324,6 +327,21 @@ int32_t tvm_all_quotients_combined(tvm_ctx* ctx, const tvm_table* main_table, co
                                    tvm_domain trace_domain, tvm_domain quotient_domain,
                                    const uint64_t* h_challenges, const uint64_t* h_weights,
                                    uint64_t* d_quotient_codeword);
+
+/* ---- the AIR on the trace itself: triton_constraints_evaluate_to_zero (stark.rs:2849-3016) on the device ----------------------
+ * Initial constraints on row 0, consistency constraints on every row, transition constraints on the rows (r, r + 1), r < n_rows - 1,
+ * terminal constraints on row n_rows - 1 -- the precondition of TVM_OPTION_AIR_VALID_TRACE.  d_main_trace [379][n_rows] words,
+ * d_aux_trace [91][n_rows][3] words (the column-major traces tvm_lde_table takes), n_rows a power of two >= 2; h_challenges: 63 XFE;
+ * seed: 32 bytes for the weights of the screen (NULL: a fixed seed).  The device screens every row with a random linear combination
+ * of its applicable constraints (a row that fails passes the screen with probability 2^-192); the host evaluates the constraints of
+ * the lowest failing rows (tvm_host_air_constraints) and reports which of them do not vanish.
+ * *failing_rows: the number of rows with at least one applicable non-zero constraint.  h_failures [capacity][2]: (row, constraint
+ * index 0..603, numbered as tvm_host_air_constraints numbers them) of the lowest failing rows, ascending by row, then by index (the
+ * last row listed may be cut short by the capacity).  *n_failures: the number of entries written.  A row the screen flags on which
+ * no applicable constraint fails on the host is an internal error (TVM_ERR_DEVICE).  Synchronises the context's stream. */
+int32_t tvm_check_constraints(tvm_ctx* ctx, const uint64_t* d_main_trace, const uint64_t* d_aux_trace, uint64_t n_rows,
+                              const uint64_t* h_challenges, const uint8_t seed[32], uint64_t capacity,
+                              uint64_t* h_failures, uint64_t* n_failures, uint64_t* failing_rows);
 
 /* ---- A3 in valid-trace mode, piecewise (for a host that distributes the evaluation over several GPUs).  The
  * constraints are generated in four classes by the length of their quotients: bit 0 = the initial / terminal quotients of degree-4

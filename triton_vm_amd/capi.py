@@ -146,7 +146,20 @@ _SIGNATURES = {
     "tvm_stdrng_streams": (C.c_int32, [C.c_void_p, C.c_char_p, C.c_uint64, C.c_uint64, C.c_void_p]),
     "tvm_bezout_coefficients": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
     "tvm_host_air_constraints": (C.c_int32, [C.c_void_p] * 6),
+    "tvm_check_constraints": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_char_p, C.c_uint64, C.c_void_p,
+                                          C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
 }
+
+# the sections of the AIR by constraint index (tvm_host_air_constraints' numbering)
+CONSTRAINT_SECTIONS = (("init", 0, 81), ("cons", 81, 178), ("tran", 178, 581), ("term", 581, 604))
+
+
+def constraint_section(index):
+    """the section ("init", "cons", "tran" or "term") of constraint `index` (0..603)"""
+    for name, a, b in CONSTRAINT_SECTIONS:
+        if a <= index < b:
+            return name
+    raise ValueError(f"constraint index {index} outside 0..603")
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 
@@ -269,6 +282,27 @@ class Context:
         one block of rows of another coset, on trace domains of at least min_rows rows (0: the library's default, 2^18)"""
         self._check(self.lib.tvm_ctx_set_option(self.handle, 7, 1 if on else 0), "tvm_ctx_set_option")
         self._check(self.lib.tvm_ctx_set_option(self.handle, 8, min_rows), "tvm_ctx_set_option")
+
+    def air_check_chunk_rows(self, rows=0):
+        """TVM_OPTION_AIR_CHECK_CHUNK_ROWS: rows per chunk of check_constraints (a power of two in 16 .. 2^20; 0: the default, 2^18)"""
+        self._check(self.lib.tvm_ctx_set_option(self.handle, 9, rows), "tvm_ctx_set_option")
+
+    def check_constraints(self, d_main_trace, d_aux_trace, n_rows, challenges, seed=None, capacity=1024):
+        """tvm_check_constraints: the AIR on the trace itself (initial constraints on row 0, consistency on every row, transition on
+        rows r, r + 1, terminal on the last row).  d_main_trace [379][n_rows] / d_aux_trace [91][n_rows][3] words on the device
+        (DeviceBuffer or pointer), challenges: 63 XFE (host), seed: 32 bytes for the screen's weights (None: a fixed seed).
+        -> (the number of failing rows, [(row, section, constraint index)] for the lowest failing rows, at most `capacity` entries)"""
+        ch = np.ascontiguousarray(challenges, dtype=np.uint64).reshape(-1)
+        assert ch.size == 63 * 3
+        if seed is not None:
+            seed = bytes(seed)
+            assert len(seed) == 32
+        out = np.zeros((max(capacity, 1), 2), np.uint64)
+        n_fail, failing = C.c_uint64(0), C.c_uint64(0)
+        ptr = lambda b: b.ptr if isinstance(b, DeviceBuffer) else b
+        self._check(self.lib.tvm_check_constraints(self.handle, ptr(d_main_trace), ptr(d_aux_trace), n_rows, ch.ctypes.data, seed, capacity,
+                                                   out.ctypes.data, C.byref(n_fail), C.byref(failing)), "tvm_check_constraints")
+        return failing.value, [(int(r), constraint_section(int(i)), int(i)) for r, i in out[:n_fail.value]]
 
     def trim(self):
         """give the cached device blocks back to the driver"""

@@ -177,7 +177,8 @@ bool fork_lanes(tvm_ctx* c) {
 }
 
 static int air_run(tvm_ctx* c, AirArgs a, u64 trace_len, u64 trace_gen, u64 q_offset, u64 q_gen, u64 index_step,
-                   const u64* d_challenges, const u64* d_weights, u64* d_out, int part_select, int accumulate);
+                   const u64* d_challenges, const u64* d_weights, u64* d_out, int part_select, int accumulate,
+                   const u64* d_zinv = nullptr);
 
 int all_quotients_combined(tvm_ctx* c, const u64* main_table, const TabLayout& layout, u64 main_w, const u64* aux_table,
                            u64 aux_w, u64 trace_len, u64 trace_gen, u64 q_offset, u64 q_gen, u64 q_len,
@@ -238,10 +239,33 @@ int air_quotients_on_block(tvm_ctx* c, const u64* main_block, u64 main_w, const 
     return air_run(c, a, trace_len, trace_gen, offset, gen, 1, d_challenges, d_weights, d_out, part_select, 0);
 }
 
+int air_on_rows(tvm_ctx* c, const u64* main_rows, u64 main_w, const u64* aux_rows, u64 aux_w, u64 n_rows, const u64* d_factors,
+                const u64* d_challenges, const u64* d_weights, u64* d_out) {
+    if (!is_pow2(n_rows)) return set_error(c, TVM_ERR_INVALID_ARGUMENT, "AIR on rows: length");
+    // one "coset" of n_rows rows of one row each: work item t is storage row t, its successor t + 1, its index t -- domain order
+    AirArgs a;
+    a.main_table = main_rows;
+    a.aux_table = aux_rows;
+    a.main_w = main_w;
+    a.aux_w = aux_w;
+    a.q_len = n_rows;
+    a.n1 = 1;
+    a.log_n1 = 0;
+    a.log_n2 = a.log_n = ilog2(n_rows);
+    a.log_xq = 0;
+    a.coset_rows = 0;
+    a.tiled = 0;
+    const u64 wider = main_w > aux_w ? main_w : aux_w;
+    if ((n_rows + 1 + TVM_RB) * wider * 8 >= (1ull << 32))
+        return set_error(c, TVM_ERR_UNSUPPORTED, "AIR on rows: beyond the 32-bit lane offsets of the AIR kernels");
+    return air_run(c, a, n_rows, TVM_ONE, TVM_ONE, TVM_ONE, 1, d_challenges, d_weights, d_out, 0, 0, d_factors);
+}
+
 // the parts selected by part_select on the rows a describes (its table pointers, shape and q_len set), the zerofier inverses of
-// the points q_offset * q_gen^index, and their scatter into d_out
+// the points q_offset * q_gen^index -- or, with d_zinv, the caller's four factors per row in their place ([4][q_len] in work order;
+// trace_len .. index_step are then unused) -- and their scatter into d_out
 static int air_run(tvm_ctx* c, AirArgs a, u64 trace_len, u64 trace_gen, u64 q_offset, u64 q_gen, u64 index_step,
-                   const u64* d_challenges, const u64* d_weights, u64* d_out, int part_select, int accumulate) {
+                   const u64* d_challenges, const u64* d_weights, u64* d_out, int part_select, int accumulate, const u64* d_zinv) {
     const u64 q_len = a.q_len;
     // Fork: a part on a short quotient domain is a few workgroups that run for the latency of its ~1000 dependent multiplications
     // (80-130 us) whatever their number; ten of them one behind the other are a millisecond of a proof that takes eight.  While one
@@ -254,14 +278,14 @@ static int air_run(tvm_ctx* c, AirArgs a, u64 trace_len, u64 trace_gen, u64 q_of
         if (!part_select || (part_select >> TVM_AIR_PART_CLASS[p] & 1)) selected[n_selected++] = p;
     int n_lanes = 1;
     if (n_selected > 1 && air_parts_fork(c, q_len) && fork_lanes(c)) n_lanes = n_selected < 4 ? n_selected : 4;
-    u64* zinv = (u64*)scratch(c, 14, (size_t)4 * q_len * sizeof(u64));
+    u64* zinv = d_zinv ? nullptr : (u64*)scratch(c, 14, (size_t)4 * q_len * sizeof(u64));
     u64* acc = (u64*)scratch(c, 23, (size_t)n_lanes * 3 * q_len * sizeof(u64));
-    if (!zinv || !acc) return set_error(c, TVM_ERR_OUT_OF_MEMORY, "zerofier inverses");
+    if ((!d_zinv && !zinv) || !acc) return set_error(c, TVM_ERR_OUT_OF_MEMORY, "zerofier inverses");
     a.challenges = d_challenges;
     a.weights = d_weights;
-    a.zinv = zinv;
+    a.zinv = d_zinv ? d_zinv : zinv;
     a.out = acc;
-    {
+    if (!d_zinv) {
         ZerofierArgs z;
         z.air = a;
         z.q_offset = q_offset;

@@ -152,6 +152,12 @@ int32_t tvm_ctx_set_option(tvm_ctx* c, int32_t option, uint64_t value) {
         c->air_remainder_min_rows = value ? value : 1ull << 18;
         return TVM_OK;
     }
+    if (option == TVM_OPTION_AIR_CHECK_CHUNK_ROWS) {
+        if (value && (!is_pow2(value) || value < TVM_RB || value > (1ull << 20)))
+            return set_error(c, TVM_ERR_INVALID_ARGUMENT, "TVM_OPTION_AIR_CHECK_CHUNK_ROWS: a power of two in 16 .. 2^20");
+        c->air_check_chunk_rows = value ? value : 1ull << 18;
+        return TVM_OK;
+    }
     if (option == TVM_OPTION_MERKLE_MIN_WORKGROUPS) {
         c->merkle_min_workgroups = value ? value : 4096;
         return TVM_OK;

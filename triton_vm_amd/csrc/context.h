@@ -128,6 +128,7 @@ struct tvm_ctx {
     u64 air_fork_max_workgroups = 256;                  // TVM_OPTION_AIR_FORK_MAX_WORKGROUPS (0 after set_option(…, 0): never fork)
     bool air_remainder_coset = true;                    // TVM_OPTION_AIR_REMAINDER_COSET (capi.hip: quotients_by_remainder_coset)
     u64 air_remainder_min_rows = 1ull << 18;            // TVM_OPTION_AIR_REMAINDER_MIN_ROWS
+    u64 air_check_chunk_rows = 1ull << 18;              // TVM_OPTION_AIR_CHECK_CHUNK_ROWS (air_check.hip: tvm_check_constraints)
 };
 
 namespace tvm {

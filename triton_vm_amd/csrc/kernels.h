@@ -66,6 +66,11 @@ int all_quotients_combined(tvm_ctx* c, const u64* main_table, const TabLayout& l
 // that order.
 int air_quotients_on_block(tvm_ctx* c, const u64* main_block, u64 main_w, const u64* aux_block, u64 aux_w, u64 n1, u64 trace_len,
                            u64 trace_gen, u64 offset, u64 gen, const u64* d_challenges, const u64* d_weights, u64* d_out, int part_select);
+// The parts on n_rows rows of one row each (rows 0 .. n_rows of main_rows / aux_rows, row-block-major, row n_rows the successor of
+// the last), with d_factors ([4][n_rows]: per row, one factor per section -- initial, consistency, transition, terminal) in place of
+// the zerofier inverses.  Out: n_rows XFE in row order (air_check.hip).
+int air_on_rows(tvm_ctx* c, const u64* main_rows, u64 main_w, const u64* aux_rows, u64 aux_w, u64 n_rows, const u64* d_factors,
+                const u64* d_challenges, const u64* d_weights, u64* d_out);
 // a quotient domain this short leaves the chip to the parts side by side (the fork lanes): the row-by-row evaluation of all ten
 // parts then costs what its longest lane does, less than valid-trace mode's six evaluations and five transforms one behind another
 bool air_parts_fork(const tvm_ctx* c, u64 q_len);

@@ -867,6 +867,9 @@ u64 estimated_bytes(const StarkParameters& p, u64 world, u64 passes) {
 std::vector<u64> prove_execution_sharded(const Context& c, const StarkParameters& p, const tvmh_comm* comm, unsigned passes, const tvm_aet& aet,
                                          const Claim& claim, const uint8_t seed[32], bool profile, std::string* stats,
                                          u64 split_tree_min_leaves, unsigned policy_first_passes) {
+    if (tvmh_get_option(TVMH_OPTION_CHECK_TRACE))
+        throw Error(TVM_ERR_UNSUPPORTED, "TVMH_OPTION_CHECK_TRACE: the sharded / coset-wise prover does not check the trace; unset the option or "
+                                         "check with tvmh_check_execution");
     const u64 n = p.trace.length;
     const CommSession session(comm, c);
     // TVMH_OPTION_TRACE: host wall time of the phases of one proof on stderr (no stream synchronisation is added)

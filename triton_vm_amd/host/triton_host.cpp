@@ -1012,6 +1012,17 @@ void ExecutionTables::extend(const Context& c, u64 n, const std::vector<Xfe>& ch
     c.check(tvm_fill_derived_aux_columns(c.raw(), main_trace.ptr(), aux_trace.ptr(), n, challenges[0].c), "tvm_fill_derived_aux_columns");
 }
 
+TraceCheck check_trace(const Context& c, const u64* d_main_trace, const u64* d_aux_trace, u64 n_rows, const std::vector<Xfe>& challenges,
+                       const uint8_t seed[32], u64 capacity) {
+    TraceCheck r;
+    r.failures.resize(2 * capacity);
+    u64 written = 0;
+    c.check(tvm_check_constraints(c.raw(), d_main_trace, d_aux_trace, n_rows, challenges[0].c, seed, capacity, r.failures.data(), &written,
+                                  &r.failing_rows), "tvm_check_constraints");
+    r.failures.resize(2 * written);
+    return r;
+}
+
 std::vector<u64> prove_execution(const Context& c, const StarkParameters& p, const tvm_aet& aet, const Claim& claim,
                                  const uint8_t seed[32]) {
     const u64 n = p.trace.length;
@@ -1019,7 +1030,23 @@ std::vector<u64> prove_execution(const Context& c, const StarkParameters& p, con
     const ExecutionTables t(c, p, aet, seed, [&](const char* what) { watch.lap(what); });
     Prover prover(c, p, t.main_trace.ptr(), t.main_rnd.ptr(), t.aux_trace.ptr(), t.aux_rnd.ptr(), t.quotient_randomizer, claim);
     prover.assume_valid_trace = !tvmh_get_option(TVMH_OPTION_EXACT_AIR);
-    prover.extend = [&](const std::vector<Xfe>& challenges) { t.extend(c, n, challenges); };
+    // TVMH_OPTION_CHECK_TRACE: valid-trace mode only on a trace that passes the AIR -- checked once the trace is complete, with the
+    // proof's own challenges and screen weights from a seed of its own (the offset after the quotient randomizer's); the proof stream
+    // is not touched, so a trace that fails gets the exact-mode proof
+    const bool check = prover.assume_valid_trace && tvmh_get_option(TVMH_OPTION_CHECK_TRACE) != 0;
+    prover.extend = [&](const std::vector<Xfe>& challenges) {
+        t.extend(c, n, challenges);
+        if (!check) return;
+        uint8_t check_seed[32];
+        offset_rng_seed(seed, NUM_MAIN + NUM_AUX + 2, check_seed);
+        const TraceCheck r = check_trace(c, t.main_trace.ptr(), t.aux_trace.ptr(), n, challenges, check_seed, 1);
+        watch.lap("constraint check");
+        if (!r.failing_rows) return;
+        prover.assume_valid_trace = false;
+        if (watch.on)
+            std::fprintf(stderr, "[tvmh] constraint check: %llu failing rows (the first: row %llu, constraint %llu): exact AIR\n",
+                         (unsigned long long)r.failing_rows, (unsigned long long)r.failures[0], (unsigned long long)r.failures[1]);
+    };
     const ProofStream stream = prover.prove();
     watch.lap("prove (extend + hot path)");
     std::vector<u64> proof = stream.proof();
@@ -1029,11 +1056,11 @@ std::vector<u64> prove_execution(const Context& c, const StarkParameters& p, con
 
 }  // namespace triton_vm
 
-static std::atomic<uint64_t> g_options[5] = {{0}, {0}, {0}, {0}, {0}};   // indexed by TVMH_OPTION_*
+static std::atomic<uint64_t> g_options[6] = {{0}, {0}, {0}, {0}, {0}, {0}};   // indexed by TVMH_OPTION_*
 extern "C" void tvmh_set_option(uint32_t option, uint64_t value) {
-    if (option >= 1 && option <= 4) g_options[option].store(value);
+    if (option >= 1 && option <= 5) g_options[option].store(value);
 }
-extern "C" uint64_t tvmh_get_option(uint32_t option) { return option >= 1 && option <= 4 ? g_options[option].load() : 0; }
+extern "C" uint64_t tvmh_get_option(uint32_t option) { return option >= 1 && option <= 5 ? g_options[option].load() : 0; }
 
 extern "C" int32_t tvmh_prove(tvm_ctx* ctx, uint32_t log2_padded_height, uint64_t num_trace_randomizers,
                               uint64_t num_collinearity_checks, uint32_t log2_expansion, const uint64_t* d_main_trace,
@@ -1102,6 +1129,53 @@ extern "C" int32_t tvmh_prove_execution(tvm_ctx* ctx, const tvm_aet* aet, uint32
         }
         if (proof_words) *proof_words = proof.size();
         if (h_proof && capacity >= proof.size()) std::memcpy(h_proof, proof.data(), proof.size() * sizeof(u64));
+        return TVM_OK;
+    } catch (const Error& e) {
+        if (error && error_capacity) std::snprintf(error, error_capacity, "%s", e.what());
+        return e.status ? e.status : TVM_ERR_INVALID_ARGUMENT;
+    } catch (const std::exception& e) {
+        if (error && error_capacity) std::snprintf(error, error_capacity, "%s", e.what());
+        return TVM_ERR_DEVICE;
+    }
+}
+
+extern "C" int32_t tvmh_check_execution(tvm_ctx* ctx, const tvm_aet* aet, uint32_t log2_padded_height, const uint8_t seed[32],
+                                        const uint64_t* h_program_digest, const uint64_t* h_public_input, uint64_t n_public_input,
+                                        const uint64_t* h_public_output, uint64_t n_public_output, uint64_t capacity, uint64_t* h_failures,
+                                        uint64_t* n_failures, uint64_t* failing_rows, char* error, uint64_t error_capacity) {
+    using namespace triton_vm;
+    try {
+        if (!aet || !seed || !n_failures || !failing_rows || (capacity && !h_failures) || log2_padded_height < 1 || log2_padded_height > 40)
+            throw Error(TVM_ERR_INVALID_ARGUMENT, "tvmh_check_execution: arguments");
+        const Context c(ctx);
+        const u64 n = 1ull << log2_padded_height;
+        Claim claim;
+        if (h_program_digest) std::memcpy(claim.program_digest, h_program_digest, sizeof(claim.program_digest));
+        if (n_public_input) claim.input.assign(h_public_input, h_public_input + n_public_input);
+        if (n_public_output) claim.output.assign(h_public_output, h_public_output + n_public_output);
+        // the trace prove_execution would prove (ExecutionTables without the trace randomizers): fill, pad, derived columns, the
+        // batch-randomizer column, extend -- with 59 challenges drawn from `seed` and the 4 the claim derives
+        DeviceBuffer main_trace(c, NUM_MAIN * n), aux_trace(c, NUM_AUX * n * 3);
+        u64 lengths[9];
+        c.check(tvm_fill_main_table(c.raw(), aet, main_trace.ptr(), n, lengths), "tvm_fill_main_table");
+        for (u64 len : lengths)
+            if (len > n) throw Error(TVM_ERR_INVALID_ARGUMENT, "a table is longer than the padded height");
+        c.check(tvm_pad_main_table(c.raw(), main_trace.ptr(), n, lengths), "tvm_pad_main_table");
+        c.check(tvm_fill_derived_main_columns(c.raw(), main_trace.ptr(), n), "tvm_fill_derived_main_columns");
+        uint8_t aux_seed[32], batch_seed[32], weight_seed[32];
+        offset_rng_seed(seed, NUM_MAIN, aux_seed);
+        offset_rng_seed(aux_seed, NUM_AUX, batch_seed);
+        offset_rng_seed(seed, NUM_MAIN + NUM_AUX + 2, weight_seed);
+        c.check(tvm_stdrng_elements(c.raw(), batch_seed, 3 * n, aux_trace.ptr() + (NUM_AUX - 1) * n * 3), "tvm_stdrng_elements");
+        std::vector<Xfe> sampled(NUM_SAMPLED_CHALLENGES);
+        tvm_host_stdrng_elements(seed, 3 * sampled.size(), sampled[0].c);
+        const std::vector<Xfe> challenges = derive_challenges(sampled, claim);
+        c.check(tvm_extend_aux_table(c.raw(), main_trace.ptr(), aux_trace.ptr(), n, challenges[0].c), "tvm_extend_aux_table");
+        c.check(tvm_fill_derived_aux_columns(c.raw(), main_trace.ptr(), aux_trace.ptr(), n, challenges[0].c), "tvm_fill_derived_aux_columns");
+        const TraceCheck r = check_trace(c, main_trace.ptr(), aux_trace.ptr(), n, challenges, weight_seed, capacity);
+        *failing_rows = r.failing_rows;
+        *n_failures = r.failures.size() / 2;
+        if (!r.failures.empty()) std::memcpy(h_failures, r.failures.data(), r.failures.size() * sizeof(u64));
         return TVM_OK;
     } catch (const Error& e) {
         if (error && error_capacity) std::snprintf(error, error_capacity, "%s", e.what());

@@ -228,6 +228,14 @@ struct ExecutionTables {
     void extend(const Context& c, u64 n_rows, const std::vector<Xfe>& challenges) const;
 };
 
+// tvm_check_constraints on a complete trace: the number of failing rows and (row, constraint index) pairs of the lowest of them
+struct TraceCheck {
+    u64 failing_rows = 0;
+    std::vector<u64> failures;   // [k][2]
+};
+TraceCheck check_trace(const Context& c, const u64* d_main_trace, const u64* d_aux_trace, u64 n_rows, const std::vector<Xfe>& challenges,
+                       const uint8_t seed[32], u64 capacity);
+
 // Prover::prove(claim, aet) from its first line (stark.rs:331-719): the master main table is filled from the algebraic
 // execution trace and padded on the device, every randomizer is drawn from `seed` the way the reference draws it
 // (master_table.rs:423-434, 1006-1024, stark.rs:1315-1322), the auxiliary table is extended on the device once the
@@ -390,6 +398,15 @@ extern "C" int32_t tvmh_prove_execution(tvm_ctx* ctx, const tvm_aet* aet, uint32
                                         uint64_t* h_proof, uint64_t proof_capacity_words, uint64_t* proof_words, char* error,
                                         uint64_t error_capacity);
 
+// Does the device's fill, pad and extend of this execution trace, with this claim, give a trace on which the AIR holds?  The trace of
+// prove_execution (without the trace randomizers), with the 59 sampled challenges drawn from `seed` (StdRng) and the 4 the claim
+// derives, checked by tvm_check_constraints (screen weights from the seed's offset NUM_MAIN + NUM_AUX + 2).  Writes the report of
+// tvm_check_constraints: *failing_rows, and (row, constraint index) pairs h_failures[capacity][2] of the lowest failing rows.  No proof.
+extern "C" int32_t tvmh_check_execution(tvm_ctx* ctx, const tvm_aet* aet, uint32_t log2_padded_height, const uint8_t seed[32],
+                                        const uint64_t* h_program_digest, const uint64_t* h_public_input, uint64_t n_public_input,
+                                        const uint64_t* h_public_output, uint64_t n_public_output, uint64_t capacity, uint64_t* h_failures,
+                                        uint64_t* n_failures, uint64_t* failing_rows, char* error, uint64_t error_capacity);
+
 // Process-wide switches of this host library.  TVMH_OPTION_EXACT_AIR != 0: prove_execution (plain and sharded) evaluates the AIR row
 // by row on every point of the quotient domain, as the reference does (master_table.rs:1264-1363), instead of in valid-trace mode
 //  -- the same proof on a valid trace; bench.py times both.
@@ -408,6 +425,11 @@ extern "C" int32_t tvmh_prove_execution(tvm_ctx* ctx, const tvm_aet* aet, uint32
 // overlaps with compute (at ~300 GB/s per rank moving a column's coefficients costs what recomputing them
 // costs); default 0 = the coset sharding alone.  k <= 16.
 #define TVMH_OPTION_COLUMN_SPLIT 4
+// TVMH_OPTION_CHECK_TRACE != 0: prove_execution checks the AIR on the padded, extended trace before it evaluates the AIR in valid-trace
+// mode (tvm_check_constraints, with the proof's challenges and screen weights drawn from the randomness seed), and proves a trace that
+// fails in exact mode -- the reference's proof, word for word -- reporting the fallback under TVMH_OPTION_TRACE.  Default 0.  The
+// sharded / coset-wise entry points (and prove_execution's fallback to them on out-of-memory) refuse it: TVM_ERR_UNSUPPORTED.
+#define TVMH_OPTION_CHECK_TRACE 5
 extern "C" void tvmh_set_option(uint32_t option, uint64_t value);
 extern "C" uint64_t tvmh_get_option(uint32_t option);
 

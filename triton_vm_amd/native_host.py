@@ -33,6 +33,10 @@ def load_host_library(backend_path=None, out=None):
     lib.tvmh_prove_sharded.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint32, C.c_void_p,
                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint64,
                                        C.POINTER(C.c_uint64), C.c_char_p, C.c_uint64]
+    lib.tvmh_check_execution.restype = C.c_int32
+    lib.tvmh_check_execution.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_char_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p,
+                                         C.c_uint64, C.c_uint64, C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_char_p,
+                                         C.c_uint64]
     lib.tvmh_set_option.restype = None
     lib.tvmh_set_option.argtypes = [C.c_uint32, C.c_uint64]
     lib.tvmh_get_option.restype = C.c_uint64
@@ -52,6 +56,24 @@ OPTION_EXACT_AIR = 1   # tvmh_set_option: prove_execution evaluates the AIR row 
 OPTION_SHARE_REPLICATED_TABLES = 2   # in-process ranks use ONE copy of the replicated trace-side tables (triton_host.hpp)
 OPTION_TRACE = 3   # host wall time of the steps of prove_execution on stderr
 OPTION_COLUMN_SPLIT = 4   # k > 0: the sharded prover splits the inverse transforms by columns, coefficients exchanged in k chunks
+OPTION_CHECK_TRACE = 5   # prove_execution checks the AIR on the trace first and proves a trace that fails in exact mode
+
+
+class host_option:
+    """`with host_option(lib, OPTION_CHECK_TRACE, 1): ...` -- a process-wide switch of the C++ host (tvmh_set_option) for the calls
+    inside the block; the previous value is restored on the way out, exception or not"""
+
+    def __init__(self, host_lib, option, value):
+        self.lib, self.option, self.value = host_lib, option, value
+
+    def __enter__(self):
+        self.previous = self.lib.tvmh_get_option(self.option)
+        self.lib.tvmh_set_option(self.option, self.value)
+        return self
+
+    def __exit__(self, *exc):
+        self.lib.tvmh_set_option(self.option, self.previous)
+        return False
 
 
 # ---- communicators for the sharded C++ host (triton_host.hpp: tvmh_comm) -----------------------------------------------
@@ -297,6 +319,25 @@ def prove_execution(ctx, host_lib, aet, padded_height, claim, randomness_seed, s
             _PROOF_BUFFERS.buffer = out               # (kept: its pages are mapped by now)
             return out[:n.value].copy()
         out = np.empty(int(n.value), np.uint64)   # the proof did not fit: grow and run again
+
+
+def check_execution(ctx, host_lib, aet, padded_height, claim, seed, capacity=1024):
+    """tvmh_check_execution: the device's fill, pad and extend of `aet` (as prove_execution builds the trace; challenges drawn from
+    `seed`, 32 bytes, and derived from `claim`), then the AIR on that trace (tvm_check_constraints).  No proof.
+    -> (the number of failing rows, [(row, section, constraint index)] of the lowest failing rows, at most `capacity` entries)"""
+    from .capi import constraint_section
+    from .master_table import aet_struct
+
+    s, keep = aet_struct(aet)
+    log2 = padded_height.bit_length() - 1
+    out = np.zeros((max(capacity, 1), 2), np.uint64)
+    err, n_fail, failing = C.create_string_buffer(512), C.c_uint64(0), C.c_uint64(0)
+    rc = host_lib.tvmh_check_execution(ctx.handle, C.addressof(s), log2, bytes(seed), claim.program_digest.ctypes.data, claim.input.ctypes.data,
+                                       claim.input.size, claim.output.ctypes.data, claim.output.size, capacity, out.ctypes.data,
+                                       C.byref(n_fail), C.byref(failing), err, len(err))
+    if rc != 0:
+        raise NativeHostError(rc, f"tvmh_check_execution failed ({rc}): {err.value.decode()}")
+    return failing.value, [(int(r), constraint_section(int(i)), int(i)) for r, i in out[:n_fail.value]]
 
 
 class NativeProver:
