@@ -494,6 +494,42 @@ int32_t tvm_verifier_deep_values(tvm_ctx* ctx, const uint64_t* h_main_rows, cons
                                  const uint64_t* h_weights_quot, const uint64_t* h_weights_deep,
                                  const uint64_t* h_ood_points, const uint64_t* h_ood_values, uint64_t* h_out);
 
+/* ---- verifier batch work outside the revealed rows (csrc/verify_ldt.hip) -------------------------------
+ * Host data in, host data out; each call stages through the context's pool, is ONE launch on the context's stream and
+ * synchronises it once.  A malformed input is a status or a per-job flag, never an abort.  Limits (TVM_ERR_UNSUPPORTED beyond): */
+#define TVM_VERIFIER_MAX_TREES 4096u                 /* jobs per tvm_verifier_merkle_roots call */
+#define TVM_VERIFIER_MAX_LEAVES (1ull << 40)         /* leaves of one tree (from 1) */
+#define TVM_VERIFIER_MAX_QUERIES (1ull << 16)        /* leaf indices per tree, FRI checks, STIR queries per call */
+#define TVM_VERIFIER_MAX_QUOTIENT_SET (1u << 20)     /* points of a STIR quotient set */
+/* MerkleTreeInclusionProof::verify [twenty-first] up to the comparison, for all trees of a proof at once: the three row openings
+ * (stark.rs:1592-1672), FRI's rounds (fri.rs:430-560), STIR's rounds (stir.rs:1157-1226).  Job j: a tree of n_leaves[j] leaves (a
+ * power of two), n_indices[j] leaf indices h_indices[j] (duplicates allowed) with their digests h_leaf_digests[j] [n][5], and the
+ * authentication structure h_auth[j] [n_auth[j]][5] in the order of MerkleTree::authentication_structure (descending heap index).
+ * Out: the recomputed root h_roots[j][5] and h_flags[j]: non-zero (root all zero) when the job is malformed -- no index, an index
+ * outside the tree, a repeated index with two digests, too few or too many authentication nodes.  The caller compares the roots.
+ * At most 64 * TVM_VERIFIER_MAX_QUERIES authentication nodes per tree and 2^31 nodes per call. */
+int32_t tvm_verifier_merkle_roots(tvm_ctx* ctx, uint32_t n_jobs, const uint64_t* n_leaves, const uint64_t* n_indices,
+                                  const uint64_t* const* h_indices, const uint64_t* const* h_leaf_digests,
+                                  const uint64_t* n_auth, const uint64_t* const* h_auth, uint64_t* h_roots, uint32_t* h_flags);
+/* All collinearity checks of all rounds of Fri::verify (fri.rs:520-560, Polynomial::get_colinear_y): query j starts from its
+ * revealed A-leaf h_a_leaves[j] at first-round index h_indices[j]; in round r it is folded with the revealed B-leaf
+ * h_b_leaves[r][j] (index + half the round's domain) at h_challenges[r]; the round's domain is first_domain.pow(2^r).
+ * h_out [n_checks][3]: the value after round n_rounds - 1, which the caller compares with the last codeword.
+ * first_domain.length >= 2^n_rounds. */
+int32_t tvm_verifier_fri_folds(tvm_ctx* ctx, tvm_domain first_domain, uint32_t n_rounds, const uint64_t* h_challenges,
+                               const uint64_t* h_indices, uint64_t n_checks, const uint64_t* h_a_leaves,
+                               const uint64_t* h_b_leaves, uint64_t* h_out);
+/* The in-domain answers of one STIR round (stir.rs:1259-1340).  Query j: the folding_factor revealed values h_values[j][ff][3] on
+ * the coset h_coset_roots[j] * kth_root^i, i < ff.  k == 0: initial_in_domain_answers -- the polynomial of degree < ff through
+ * them at h_folding_randomness.  k > 0: subsequent_in_domain_answers -- the values first go through the previous round's quotient
+ * (value - Ans(x)) / prod_i (x - h_quotient_set[i]) and degree correction sum_{e <= k} (rc x)^e (with its rc x = 1 branch);
+ * h_answer_polynomial: the k coefficients of Ans (tvm_xfe_interpolate over the quotient set).  h_out [n_queries][3].
+ * folding_factor <= 16; kth_root of order >= folding_factor. */
+int32_t tvm_verifier_stir_answers(tvm_ctx* ctx, uint32_t folding_factor, uint64_t n_queries, const uint64_t* h_values,
+                                  const uint64_t* h_coset_roots, uint64_t kth_root, const uint64_t* h_folding_randomness,
+                                  uint32_t k, const uint64_t* h_quotient_set, const uint64_t* h_answer_polynomial,
+                                  const uint64_t* h_degree_correction_randomness, uint64_t* h_out);
+
 /* host: the 604 AIR constraints on ONE row pair whose main rows are XFieldElements -- what Verifier::verify evaluates on the
  * out-of-domain rows (stark.rs:1466-1491; MasterAuxTable::evaluate_{initial,consistency,transition,terminal}_constraints in
  * this order).  h_main_* [379][3], h_aux_* [91][3], h_challenges [63][3]; h_out [604][3]: initial (81), consistency (97),

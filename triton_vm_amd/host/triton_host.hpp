@@ -243,7 +243,83 @@ TraceCheck check_trace(const Context& c, const u64* d_main_trace, const u64* d_a
 std::vector<u64> prove_execution(const Context& c, const StarkParameters& p, const tvm_aet& aet, const Claim& claim,
                                  const uint8_t seed[32]);
 
+// ---- the verifier (verifier.cpp) ---------------------------------------------------------------------------------------
+// The verdict of a verification: 0 = accepted, otherwise one code per variant of VerificationError / LdtVerificationError /
+// ProofStreamError (error.rs); verdict_name gives the variant's name, as triton_vm_amd/verifier.py raises it.
+enum Verdict : uint32_t {
+    VERDICT_ACCEPTED = 0,
+    VERDICT_PROOF_DECODING_ERROR = 1,   // ProofStreamError::DecodingError
+    VERDICT_PROOF_STREAM_ERROR = 2,     // ProofStreamError::EmptyQueue, ProofItem::try_into_* on another variant
+    VERDICT_LOG2_PADDED_HEIGHT_TOO_LARGE = 3,
+    VERDICT_OUT_OF_DOMAIN_QUOTIENT_VALUE_MISMATCH = 4,
+    VERDICT_INCORRECT_NUMBER_OF_ROW_INDICES = 5,
+    VERDICT_INCORRECT_NUMBER_OF_MAIN_ROWS = 6,
+    VERDICT_INCORRECT_NUMBER_OF_AUX_ROWS = 7,
+    VERDICT_INCORRECT_NUMBER_OF_QUOTIENT_SEGMENT_ELEMENTS = 8,
+    VERDICT_MAIN_CODEWORD_AUTHENTICATION_FAILURE = 9,
+    VERDICT_AUX_CODEWORD_AUTHENTICATION_FAILURE = 10,
+    VERDICT_QUOTIENT_CODEWORD_AUTHENTICATION_FAILURE = 11,
+    VERDICT_COMBINATION_CODEWORD_MISMATCH = 12,
+    VERDICT_SUPERFLUOUS_PROOF_ITEMS = 13,
+    VERDICT_BAD_MERKLE_AUTHENTICATION_PATH = 20,   // LdtVerificationError from here on
+    VERDICT_INCORRECT_NUMBER_OF_REVEALED_LEAVES = 21,
+    VERDICT_LAST_CODEWORD_MISMATCH = 22,
+    VERDICT_BAD_MERKLE_ROOT_FOR_LAST_CODEWORD = 23,
+    VERDICT_LAST_ROUND_POLYNOMIAL_HAS_TOO_HIGH_DEGREE = 24,
+    VERDICT_LAST_ROUND_POLYNOMIAL_EVALUATION_MISMATCH = 25,
+    VERDICT_INCORRECT_NUMBER_OF_OUT_OF_DOMAIN_VALUES = 26,
+    VERDICT_REPEATED_INTERPOLATION_POINT = 27,
+    VERDICT_UNSUPPORTED_PARAMETERS = 28,   // the proof states a padded height this host derives no parameters for
+};
+const char* verdict_name(uint32_t verdict);
+struct VerificationFailure : std::runtime_error {
+    uint32_t verdict;
+    explicit VerificationFailure(uint32_t v) : std::runtime_error(verdict_name(v)), verdict(v) {}
+};
+
+// One ProofItem of a decoded proof (proof_item.rs:96-150): positions are word offsets into the proof.  [at, at + size) is the
+// item's encoding (discriminant first); a response holds its leaves (a StirResponse: n_stacks stacks of stack_height elements)
+// and the place of its authentication structure.
+struct DecodedItem {
+    int variant = 0;
+    u64 at = 0, size = 0, payload_at = 0, payload_words = 0, auth_at = 0, auth_words = 0, stack_height = 0, n_stacks = 0;
+    std::vector<u64> leaves;
+};
+// ProofStream::try_from(&Proof) (proof_stream.rs:106-113): throws VerificationFailure(VERDICT_PROOF_DECODING_ERROR)
+std::vector<DecodedItem> decode_proof(const u64* proof_words, u64 n_words);
+u64 proof_padded_height(const u64* proof_words, u64 n_words);   // Proof::padded_height (proof.rs:45-59)
+
+// Verifier::verify (stark.rs:1388-1763).  ldt_choice as tvmh_prove_execution takes it: 0 = FRI, 1 = STIR, 2 = Stark::ldt's rule.
+class Verifier {
+public:
+    enum Stage { STAGE_DECODE, STAGE_TRANSCRIPT_AIR, STAGE_LDT, STAGE_INCLUSION, STAGE_ROW_DIGESTS, STAGE_DEEP_VALUES, NUM_STAGES };
+    Verifier(const Context& c, unsigned security_level = 160, unsigned log2_expansion = 2, unsigned ldt_choice = 2)
+        : c_(c), security_level_(security_level), log2_expansion_(log2_expansion), ldt_choice_(ldt_choice) {}
+    // the revealed first-round indices on acceptance; throws VerificationFailure on rejection, Error on a device failure
+    std::vector<u64> verify(const Claim& claim, const u64* proof_words, u64 n_words);
+    double stage_ms[NUM_STAGES] = {};   // host wall time of the last verify(), by stage
+
+private:
+    const Context& c_;
+    unsigned security_level_, log2_expansion_, ldt_choice_;
+};
+
 }  // namespace triton_vm
+
+// Verifier::verify for hosts without a C++ ABI.  Returns TVM_OK when the procedure ran to a verdict: *verdict is 0 (accepted) or a
+// triton_vm::Verdict code, with the variant's name in `error`; a rejection is not an error status (TVM_ERR_* is for bad arguments
+// and device failures).  On acceptance the revealed first-round indices go to h_indices (copied when indices_capacity suffices;
+// *n_indices is their number).  The claim: program digest (5 words, null = zeros), version (proof.rs:33: 6), public input and output.
+// stage_ms: null, or room for six doubles -- decode, transcript and out-of-domain AIR, low-degree test, Merkle inclusion, row
+// digests, DEEP values (host wall time).
+extern "C" int32_t tvmh_verify(tvm_ctx* ctx, const uint64_t* h_proof, uint64_t proof_words, const uint64_t* h_program_digest,
+                               uint32_t version, const uint64_t* h_public_input, uint64_t n_public_input,
+                               const uint64_t* h_public_output, uint64_t n_public_output, uint32_t security_level,
+                               uint32_t log2_expansion, uint32_t ldt_choice, uint32_t* verdict, uint64_t* h_indices,
+                               uint64_t indices_capacity, uint64_t* n_indices, double* stage_ms, char* error, uint64_t error_capacity);
+// Proof::padded_height: *verdict 0 and the height, or the decoding verdict
+extern "C" int32_t tvmh_proof_padded_height(const uint64_t* h_proof, uint64_t proof_words, uint32_t* verdict, uint64_t* padded_height);
+extern "C" const char* tvmh_verdict_name(uint32_t verdict);
 
 // ---- one proof over the GPUs of a node, and/or coset by coset (sharded_host.cpp) ----------------------------------------
 // The collectives the sharded prover needs, as a table of functions so that this library stays free of device code and of

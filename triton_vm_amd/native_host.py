@@ -37,6 +37,14 @@ def load_host_library(backend_path=None, out=None):
     lib.tvmh_check_execution.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_char_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p,
                                          C.c_uint64, C.c_uint64, C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_char_p,
                                          C.c_uint64]
+    lib.tvmh_verify.restype = C.c_int32
+    lib.tvmh_verify.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64,
+                                C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64),
+                                C.c_void_p, C.c_char_p, C.c_uint64]
+    lib.tvmh_proof_padded_height.restype = C.c_int32
+    lib.tvmh_proof_padded_height.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]
+    lib.tvmh_verdict_name.restype = C.c_char_p
+    lib.tvmh_verdict_name.argtypes = [C.c_uint32]
     lib.tvmh_set_option.restype = None
     lib.tvmh_set_option.argtypes = [C.c_uint32, C.c_uint64]
     lib.tvmh_get_option.restype = C.c_uint64
@@ -338,6 +346,50 @@ def check_execution(ctx, host_lib, aet, padded_height, claim, seed, capacity=102
     if rc != 0:
         raise NativeHostError(rc, f"tvmh_check_execution failed ({rc}): {err.value.decode()}")
     return failing.value, [(int(r), constraint_section(int(i)), int(i)) for r, i in out[:n_fail.value]]
+
+
+VERIFY_STAGES = ("decode", "transcript and out-of-domain AIR", "low-degree test", "Merkle inclusion", "row digests", "DEEP values")
+
+
+def verify_verdict(ctx, host_lib, claim, proof_words, security_level=160, log2_expansion=2, ldt=None):
+    """tvmh_verify as it is: -> (status, verdict code, variant name, indices, {stage: ms}); no exception for a rejection"""
+    words = np.ascontiguousarray(proof_words, dtype=np.uint64).reshape(-1)
+    digest = np.ascontiguousarray(claim.program_digest, dtype=np.uint64)
+    public_input, output = np.ascontiguousarray(claim.input, dtype=np.uint64), np.ascontiguousarray(claim.output, dtype=np.uint64)
+    verdict, n, err = C.c_uint32(0xFFFFFFFF), C.c_uint64(0), C.create_string_buffer(256)
+    indices, stages = np.zeros(1 << 12, np.uint64), np.zeros(len(VERIFY_STAGES), np.float64)
+    rc = host_lib.tvmh_verify(ctx.handle, words.ctypes.data, words.size, digest.ctypes.data, claim.version, public_input.ctypes.data,
+                              public_input.size, output.ctypes.data, output.size, security_level, log2_expansion,
+                              {"fri": 0, "stir": 1, None: 2}[ldt], C.byref(verdict), indices.ctypes.data, indices.size, C.byref(n),
+                              stages.ctypes.data, err, len(err))
+    return rc, verdict.value, err.value.decode(), [int(i) for i in indices[:min(n.value, indices.size)]], dict(zip(VERIFY_STAGES, stages.tolist()))
+
+
+def verify(ctx, host_lib, claim, proof_words, security_level=160, log2_expansion=2, ldt=None):
+    """The C++ host's Verifier::verify (triton_vm::Verifier, host/verifier.cpp) with the per-query work on the device.  claim: a
+    proof_stream.Claim; ldt: "fri", "stir" or None = Stark::ldt's rule.  -> the revealed first-round indices; raises
+    verifier.VerificationError carrying the variant's name on a rejection, NativeHostError on a bad argument or a device failure."""
+    from .verifier import VerificationError
+
+    rc, verdict, name, indices, _ = verify_verdict(ctx, host_lib, claim, proof_words, security_level, log2_expansion, ldt)
+    if rc != 0:
+        raise NativeHostError(rc, f"tvmh_verify failed ({rc}): {name}")
+    if verdict != 0:
+        raise VerificationError(name)
+    return indices
+
+
+def proof_padded_height(host_lib, proof_words):
+    """Proof::padded_height through the C++ decoder (proof.rs:45-59); raises proof_stream.ProofDecodingError"""
+    from .proof_stream import ProofDecodingError
+
+    words = np.ascontiguousarray(proof_words, dtype=np.uint64).reshape(-1)
+    verdict, height = C.c_uint32(0), C.c_uint64(0)
+    if host_lib.tvmh_proof_padded_height(words.ctypes.data, words.size, C.byref(verdict), C.byref(height)) != 0:
+        raise RuntimeError("tvmh_proof_padded_height failed")
+    if verdict.value:
+        raise ProofDecodingError(host_lib.tvmh_verdict_name(verdict.value).decode())
+    return int(height.value)
 
 
 class NativeProver:
