@@ -37,6 +37,7 @@ extern "C" {
 #define TVM_ERR_OUT_OF_MEMORY 2    /* ProvingError::OutOfMemory -- recoverable */
 #define TVM_ERR_DEVICE 3           /* HIP runtime failure */
 #define TVM_ERR_UNSUPPORTED 4
+#define TVM_NOT_APPLICABLE 5       /* not an error: this entry point does not cover these arguments, nothing was written; call the general one */
 
 typedef struct tvm_ctx tvm_ctx;
 typedef struct tvm_table tvm_table; /* device-resident low-degree-extended master table */
@@ -65,7 +66,8 @@ int32_t tvm_ctx_trim(tvm_ctx* ctx);
  * execution trace -- what Prover::prove is for.  tvm_all_quotients_combined may then use that the constraint quotients
  * are polynomials of known degree: the consistency / transition constraints are evaluated on half of the quotient
  * domain and the codeword completed by interpolation; bit-identical to the row-by-row evaluation on a valid trace,
- * different on an invalid one (where both yield a proof the verifier rejects). */
+ * different on an invalid one (where both yield a proof the verifier rejects).  A quotient domain short enough for
+ * TVM_OPTION_AIR_FORK_MAX_WORKGROUPS (the parts side by side) disables this split: such a domain is evaluated row by row. */
 #define TVM_OPTION_AIR_VALID_TRACE 1
 /* Tuning values (per context; they change launch shapes, never results).  TVM_OPTION_LDE_CHUNK_COLUMNS: columns per chunk of
  * tvm_lde_table's three-pass transform, 0 (default) = 96 while the chunk's intermediates fit comfortably, else 32.
@@ -328,6 +330,20 @@ int32_t tvm_all_quotients_combined(tvm_ctx* ctx, const tvm_table* main_table, co
                                    const uint64_t* h_challenges, const uint64_t* h_weights,
                                    uint64_t* d_quotient_codeword);
 
+/* The same quotient as COEFFICIENTS, for the prover that only needs the segments (tvm_quotient_segments_from_coefficients): where
+ * valid-trace mode evaluates the classes on cosets of the trace domain plus a remainder block (TVM_OPTION_AIR_VALID_TRACE and
+ * TVM_OPTION_AIR_REMAINDER_COSET hold, the trace has at least TVM_OPTION_AIR_REMAINDER_MIN_ROWS rows, the tables were extended onto the
+ * quotient domain, every class's quotient fits), the sum of the classes' quotients exists in coefficient form before any codeword does,
+ * and the initial / terminal quotients of the degree-4 constraints are obtained the same way (four cosets and a block of a fifth).
+ * d_coeffs: capacity XFE, at least 4 * trace_domain.length + n1 (n1 = the rows of one block of the tables; quotient_domain.length always
+ * suffices); *n_coeffs: the number written -- every coefficient of the quotient beyond it is zero.  Evaluated on the quotient domain they
+ * are the codeword of tvm_all_quotients_combined, word for word (valid trace).  TVM_NOT_APPLICABLE, *n_coeffs = 0 and nothing written
+ * where those conditions do not hold: call tvm_all_quotients_combined. */
+int32_t tvm_all_quotients_coefficients(tvm_ctx* ctx, const tvm_table* main_table, const tvm_table* aux_table,
+                                       tvm_domain trace_domain, tvm_domain quotient_domain,
+                                       const uint64_t* h_challenges, const uint64_t* h_weights,
+                                       uint64_t* d_coeffs, uint64_t capacity, uint64_t* n_coeffs);
+
 /* ---- the AIR on the trace itself: triton_constraints_evaluate_to_zero (stark.rs:2849-3016) on the device ----------------------
  * Initial constraints on row 0, consistency constraints on every row, transition constraints on the rows (r, r + 1), r < n_rows - 1,
  * terminal constraints on row n_rows - 1 -- the precondition of TVM_OPTION_AIR_VALID_TRACE.  d_main_trace [379][n_rows] words,
@@ -375,6 +391,11 @@ int32_t tvm_coset_values_to_coefficients(tvm_ctx* ctx, tvm_domain trace_domain, 
 int32_t tvm_quotient_segments(tvm_ctx* ctx, const uint64_t* d_quotient_codeword, tvm_domain quotient_domain,
                               tvm_domain ldt_domain, const uint64_t* h_randomizer, uint64_t n_rand, uint64_t zeta,
                               tvm_table** out_table, uint64_t* d_polys, uint64_t poly_len);
+/* The same from the quotient's coefficients (tvm_all_quotients_coefficients): d_coeffs n_coeffs XFE, the coefficients beyond them zero;
+ * poly_len >= max(ceil(n_coeffs / 4), n_rand).  What tvm_quotient_segments does after interpolating its codeword. */
+int32_t tvm_quotient_segments_from_coefficients(tvm_ctx* ctx, const uint64_t* d_coeffs, uint64_t n_coeffs, tvm_domain ldt_domain,
+                                                const uint64_t* h_randomizer, uint64_t n_rand, uint64_t zeta,
+                                                tvm_table** out_table, uint64_t* d_polys, uint64_t poly_len);
 /* row-wise linear combination of a table's columns over its ldt-domain view: d_out[i] = sum_c w_c * cell(i, c)
  * (the P and R combinations of the randomized segments, stark.rs:520-540).  h_weights: n_cols XFE. */
 int32_t tvm_table_linear_combination(tvm_ctx* ctx, const tvm_table* table, uint64_t ldt_length,

@@ -25,6 +25,7 @@ const char* tvm_status_string(int32_t s) {
         case TVM_ERR_OUT_OF_MEMORY: return "device out of memory";
         case TVM_ERR_DEVICE: return "HIP runtime error";
         case TVM_ERR_UNSUPPORTED: return "unsupported size or configuration";
+        case TVM_NOT_APPLICABLE: return "not applicable to these arguments";
         default: return "unknown status";
     }
 }
@@ -642,22 +643,23 @@ static const u64* stage_small(tvm_ctx* c, int slot, const u64* h, size_t words) 
 struct ThreeCosetWeights {
     u64 w[9];
 };
-// coeffs[i * N + t] += sum_j w[4 i + j] * q_j[t]  (i, j < n <= 4; t < N; XFE vectors q_j, base-field weights): the polynomial
-// sum_i X^(iN) A_i from its restrictions Q_j = sum_i c_j^i A_i to n cosets (w = the inverse Vandermonde matrix)
+// coeffs[i * N + t] (+)= sum_j w[4 i + j] * q_j[t]  (i, j < n <= 4; t < N; XFE vectors q_j, base-field weights): the polynomial
+// sum_i X^(iN) A_i from its restrictions Q_j = sum_i c_j^i A_i to n cosets (w = the inverse Vandermonde matrix); added to coeffs, or
+// (accumulate = 0) stored -- the first summand of an array that is then never cleared
 struct CosetCombineWeights {
     u64 w[16];
 };
 struct CosetCombinePointers {
     const u64* q[4];
 };
-__global__ void k_coset_combine(CosetCombinePointers p, int n, u64 N, CosetCombineWeights m, u64* __restrict__ coeffs) {
+__global__ void k_coset_combine(CosetCombinePointers p, int n, u64 N, CosetCombineWeights m, u64* __restrict__ coeffs, int accumulate) {
     const u64 t = (u64)blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= N) return;
     xfe v[4];
     for (int j = 0; j < n; j++) v[j] = xfe_make(p.q[j][3 * t], p.q[j][3 * t + 1], p.q[j][3 * t + 2]);
     for (int i = 0; i < n; i++) {
         u64* o = coeffs + 3 * ((u64)i * N + t);
-        xfe acc = xfe_make(o[0], o[1], o[2]);
+        xfe acc = accumulate ? xfe_make(o[0], o[1], o[2]) : xfe_zero();
         for (int j = 0; j < n; j++) acc = xfe_add(acc, xfe_mul_bfe(v[j], m.w[4 * i + j]));
         o[0] = acc.c0, o[1] = acc.c1, o[2] = acc.c2;
     }
@@ -708,7 +710,7 @@ __global__ void k_remainder_fold(RemainderFold f, u64 M, u64 G, u64 R, u64 d, u6
 }
 // b = p[i] - sum_g partial[g][i] (the interpolant of q - R on the remainder set, i < M);  coeffs[i + k N] += v[k] * b, k < n_v
 struct RemainderScatter {
-    u64 v[4];
+    u64 v[5];
     int n_v;
 };
 __global__ void k_remainder_scatter(const u64* __restrict__ p, const u64* __restrict__ partial, u64 G, u64 M, u64 N, RemainderScatter w,
@@ -843,19 +845,14 @@ int32_t tvm_evaluate_polys_at_points(tvm_ctx* c, const uint64_t* d_coeffs, uint6
     return TVM_OK;
 }
 
-int32_t tvm_quotient_segments(tvm_ctx* c, const uint64_t* d_cw, tvm_domain qd, tvm_domain ldt, const uint64_t* h_rnd,
-                              uint64_t n_rand, uint64_t zeta, tvm_table** out_table, uint64_t* d_polys, uint64_t poly_len) {
-    if (!c || !out_table) return TVM_ERR_INVALID_ARGUMENT;
-    *out_table = nullptr;
-    if (!d_cw || !d_polys || (n_rand && !h_rnd) || !valid_domain(qd) || !valid_domain(ldt) || qd.length < 4 ||
-        poly_len < qd.length / 4 || poly_len < n_rand || ldt.length < 2)
-        return set_error(c, TVM_ERR_INVALID_ARGUMENT, "quotient_segments arguments");
-    const u64 Q = qd.length, L = ldt.length;
-    u64* coeffs = (u64*)scratch(c, 11, Q * 3 * sizeof(u64));
-    const u64* d_rnd = stage_small(c, 9, h_rnd, 3 * (size_t)n_rand);
-    if (!coeffs || !d_rnd) return set_error(c, TVM_ERR_OUT_OF_MEMORY, "segments scratch");
-    TVM_TRY(tvm_interpolate(c, 3, d_cw, qd, coeffs));
-    TVM_TRY(randomized_segments(c, coeffs, Q, d_rnd, n_rand, zeta, poly_len, d_polys));
+}  // extern "C"
+
+// The body of tvm_quotient_segments and tvm_quotient_segments_from_coefficients: the quotient's n_coeffs coefficients (zero beyond
+// them) -> the randomized segment polynomials and their table on the LDT domain.
+static int quotient_segments_of_coefficients(tvm_ctx* c, const u64* coeffs, u64 n_coeffs, tvm_domain ldt, const u64* d_rnd, u64 n_rand,
+                                             u64 zeta, tvm_table** out_table, u64* d_polys, u64 poly_len) {
+    const u64 L = ldt.length;
+    TVM_TRY(randomized_segments(c, coeffs, n_coeffs, d_rnd, n_rand, zeta, poly_len, d_polys));
     u64 M = 2;
     while (M < poly_len) M <<= 1;
     const u64* polys_in = d_polys;       // what is evaluated: the segment polynomials, or their reductions below
@@ -920,6 +917,35 @@ int32_t tvm_quotient_segments(tvm_ctx* c, const uint64_t* d_cw, tvm_domain qd, t
     }
     *out_table = t;
     return TVM_OK;
+}
+
+extern "C" {
+int32_t tvm_quotient_segments(tvm_ctx* c, const uint64_t* d_cw, tvm_domain qd, tvm_domain ldt, const uint64_t* h_rnd,
+                              uint64_t n_rand, uint64_t zeta, tvm_table** out_table, uint64_t* d_polys, uint64_t poly_len) {
+    if (!c || !out_table) return TVM_ERR_INVALID_ARGUMENT;
+    *out_table = nullptr;
+    if (!d_cw || !d_polys || (n_rand && !h_rnd) || !valid_domain(qd) || !valid_domain(ldt) || qd.length < 4 ||
+        poly_len < qd.length / 4 || poly_len < n_rand || ldt.length < 2)
+        return set_error(c, TVM_ERR_INVALID_ARGUMENT, "quotient_segments arguments");
+    const u64 Q = qd.length;
+    u64* coeffs = (u64*)scratch(c, 11, Q * 3 * sizeof(u64));
+    const u64* d_rnd = stage_small(c, 9, h_rnd, 3 * (size_t)n_rand);
+    if (!coeffs || !d_rnd) return set_error(c, TVM_ERR_OUT_OF_MEMORY, "segments scratch");
+    TVM_TRY(tvm_interpolate(c, 3, d_cw, qd, coeffs));
+    return quotient_segments_of_coefficients(c, coeffs, Q, ldt, d_rnd, n_rand, zeta, out_table, d_polys, poly_len);
+}
+
+int32_t tvm_quotient_segments_from_coefficients(tvm_ctx* c, const uint64_t* d_coeffs, uint64_t n_coeffs, tvm_domain ldt,
+                                                const uint64_t* h_rnd, uint64_t n_rand, uint64_t zeta, tvm_table** out_table,
+                                                uint64_t* d_polys, uint64_t poly_len) {
+    if (!c || !out_table) return TVM_ERR_INVALID_ARGUMENT;
+    *out_table = nullptr;
+    if (!d_coeffs || !d_polys || (n_rand && !h_rnd) || !valid_domain(ldt) || !n_coeffs || poly_len < (n_coeffs + 3) / 4 ||
+        poly_len < n_rand || ldt.length < 2)
+        return set_error(c, TVM_ERR_INVALID_ARGUMENT, "quotient_segments_from_coefficients arguments");
+    const u64* d_rnd = stage_small(c, 9, h_rnd, 3 * (size_t)n_rand);
+    if (!d_rnd) return set_error(c, TVM_ERR_OUT_OF_MEMORY, "segments scratch");
+    return quotient_segments_of_coefficients(c, d_coeffs, n_coeffs, ldt, d_rnd, n_rand, zeta, out_table, d_polys, poly_len);
 }
 
 int32_t tvm_table_linear_combination(tvm_ctx* c, const tvm_table* t, uint64_t ldt_length, const uint64_t* h_w, uint64_t* d_out) {
@@ -1029,35 +1055,42 @@ int32_t tvm_extend_aux_table(tvm_ctx* c, const uint64_t* d_main_trace, uint64_t*
 // and V the constant beta = prod (c'' - c_k); R restricted to gamma_T <w_N> is sum_k L_k(c'') Q_k (L_k the Lagrange basis in the c_k),
 // which modulo X^M - tau^M is the interpolant of R on T (k_remainder_fold).  So B = (interpolant of q on T - that fold) / beta, and V B
 // adds v_i / beta times it at the coefficients i N + (0 .. M-1) (k_remainder_scatter).  On a valid trace B's coefficients s .. M-1 are zero.
+// Class 0 (the initial / terminal quotients of the four degree-4 constraints: fewer than 4 (m - 1) + 1 <= 4N + M coefficients) goes the
+// same way when the caller wants COEFFICIENTS (tvm_all_quotients_coefficients): S = the cosets 0, 2, 4, 6 and T block 0 of coset 1 (the
+// even cosets are used up; the tables hold all eight) -- half the rows of the row-by-row evaluation on the quotient domain, and no
+// codeword of 8N points on the way.  The coefficient array is then 4N + M long.
 namespace tvm {
-static int quotients_by_remainder_coset(tvm_ctx* c, const tvm_table* mt, const tvm_table* at, tvm_domain td, tvm_domain qd, const u64* d_ch,
-                                        const u64* d_w, u64* d_out) {
+// coeffs: [4N] XFE (classes 1, 3, 2), or [4N + M] with class 0; every element is written
+static int remainder_coset_coefficients(tvm_ctx* c, const tvm_table* mt, const tvm_table* at, tvm_domain td, tvm_domain qd, const u64* d_ch,
+                                        const u64* d_w, bool with_class_0, u64* coeffs) {
     const u64 N = td.length, M = mt->layout.n1, n2 = mt->layout.n2, pitch = mt->layout.pitch, X = qd.length / N;
     const u64 G = n2 < 64 ? n2 : 64, R = n2 / G;   // the fold: G partial sums of R chunks of M coefficients
-    PoolBlock block(c, (size_t)3 * (4 * N + N + 3 * N + 2 * M + G * M) * sizeof(u64));   // released on every exit path
-    u64* coeffs = (u64*)block.p;   // [4N] XFE: the sum of the classes' quotients
-    if (!coeffs) return set_error(c, TVM_ERR_OUT_OF_MEMORY, "quotient scratch");
-    u64* vals = coeffs + 12 * N;   // [N] XFE: a class on one coset
-    u64* q = vals + 3 * N;         // [3][N] XFE: its interpolants Q_k
-    u64* q_t = q + 9 * N;          // [M] XFE: a class on T, then ...
+    const u64 n_q = with_class_0 ? 4 : 3, n_coeffs = with_class_0 ? 4 * N + M : 4 * N;
+    PoolBlock block(c, (size_t)3 * (N + n_q * N + 2 * M + G * M) * sizeof(u64));   // released on every exit path
+    u64* vals = (u64*)block.p;     // [N] XFE: a class on one coset
+    if (!vals) return set_error(c, TVM_ERR_OUT_OF_MEMORY, "quotient scratch");
+    u64* q = vals + 3 * N;         // [n_q][N] XFE: its interpolants Q_k
+    u64* q_t = q + 3 * n_q * N;    // [M] XFE: a class on T, then ...
     u64* p_t = q_t + 3 * M;        // ... its interpolant there
     u64* partial = p_t + 3 * M;    // [G][M] XFE
-    TVM_HIP_CHECK(c, hipMemsetAsync(coeffs, 0, (size_t)12 * N * sizeof(u64), c->stream));
     const u64 g_n = bfe_pow(qd.generator, X), g_m = bfe_pow(g_n, n2);
     // (the cosets of the tables ARE those of the quotient domain here: the gate asks for X == layout.X)
-    const u64 k_t = 6, gamma_t = bfe_mul(qd.offset, bfe_pow(qd.generator, k_t)), c_t = bfe_pow(gamma_t, N), d_t = bfe_pow(gamma_t, M);
-    const u64* main_t = mt->data + tvm_tab_idx(k_t * pitch, 0, (u64)mt->W);
-    const u64* aux_t = at->data + tvm_tab_idx(k_t * pitch, 0, (u64)at->W);
     TabLayout lm = mt->layout;   // one coset of the tables: a table of its own
     lm.X = 1;
     lm.log_x = 0;
-    const int CLASS_HALF = 1 << 1, CLASS_QUARTER = 1 << 2, CLASS_THREE = 1 << 3;
+    const int CLASS_FULL = 1 << 0, CLASS_HALF = 1 << 1, CLASS_QUARTER = 1 << 2, CLASS_THREE = 1 << 3;
     struct {
         int mask;
-        uint32_t n;
-    } const classes[3] = {{CLASS_HALF, 3}, {CLASS_THREE, 2}, {CLASS_QUARTER, 1}};   // S = cosets 0, 2, 4 (the first n of them)
+        uint32_t n;   // S = the first n of the cosets 0, 2, 4, 6
+        u64 k_t;      // T = block 0 of this coset
+    } const classes[4] = {{CLASS_FULL, 4, 1}, {CLASS_HALF, 3, 6}, {CLASS_THREE, 2, 6}, {CLASS_QUARTER, 1, 6}};
+    bool first = true;
     for (const auto& cl : classes) {
-        u64 cs[3];
+        if (cl.mask == CLASS_FULL && !with_class_0) continue;
+        const u64 gamma_t = bfe_mul(qd.offset, bfe_pow(qd.generator, cl.k_t)), c_t = bfe_pow(gamma_t, N), d_t = bfe_pow(gamma_t, M);
+        const u64* main_t = mt->data + tvm_tab_idx(cl.k_t * pitch, 0, (u64)mt->W);
+        const u64* aux_t = at->data + tvm_tab_idx(cl.k_t * pitch, 0, (u64)at->W);
+        u64 cs[4];
         CosetCombinePointers ptrs;
         for (uint32_t j = 0; j < 4; j++) ptrs.q[j] = nullptr;
         for (uint32_t j = 0; j < cl.n; j++) {
@@ -1072,7 +1105,10 @@ static int quotients_by_remainder_coset(tvm_ctx* c, const tvm_table* mt, const t
         }
         CosetCombineWeights w;
         if (!coset_combine_weights(cs, cl.n, w)) return set_error(c, TVM_ERR_INVALID_ARGUMENT, "quotients: two cosets with the same X^N");
-        TVM_LAUNCH(k_coset_combine, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, c->stream, ptrs, (int)cl.n, N, w, coeffs);   // += R
+        // (+)= R: the first class stores its n blocks and the rest of the array is cleared -- no pass over all of it beforehand
+        TVM_LAUNCH(k_coset_combine, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, c->stream, ptrs, (int)cl.n, N, w, coeffs, first ? 0 : 1);
+        if (first) TVM_HIP_CHECK(c, hipMemsetAsync(coeffs + 3 * cl.n * N, 0, (size_t)3 * (n_coeffs - cl.n * N) * sizeof(u64), c->stream));
+        first = false;
         // R on T, modulo X^M - tau^M: the Lagrange weights L_j(c'') = sum_i c''^i w[4 i + j]
         RemainderFold f;
         f.n = (int)cl.n;
@@ -1092,7 +1128,7 @@ static int quotients_by_remainder_coset(tvm_ctx* c, const tvm_table* mt, const t
         RemainderScatter v;
         v.n_v = (int)cl.n + 1;
         u64 beta = TVM_ONE;
-        for (int i = 0; i < 4; i++) v.v[i] = 0;
+        for (int i = 0; i < 5; i++) v.v[i] = 0;
         v.v[0] = TVM_ONE;
         for (uint32_t j = 0; j < cl.n; j++) {
             for (int e = (int)j + 1; e >= 1; e--) v.v[e] = bfe_sub(v.v[e - 1], bfe_mul(v.v[e], cs[j]));
@@ -1104,27 +1140,55 @@ static int quotients_by_remainder_coset(tvm_ctx* c, const tvm_table* mt, const t
         TVM_LAUNCH(k_remainder_scatter, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, c->stream, p_t, partial, G, M, N, v, coeffs);
         TVM_HIP_CHECK(c, hipGetLastError());
     }
+    return TVM_OK;
+}
+
+// the codeword: the coefficients of classes 1, 3, 2 evaluated on the quotient domain, class 0 added row by row
+static int quotients_by_remainder_coset(tvm_ctx* c, const tvm_table* mt, const tvm_table* at, tvm_domain td, tvm_domain qd, const u64* d_ch,
+                                        const u64* d_w, u64* d_out) {
+    const u64 N = td.length;
+    PoolBlock block(c, (size_t)12 * N * sizeof(u64));   // released on every exit path
+    u64* coeffs = (u64*)block.p;   // [4N] XFE: the sum of the classes' quotients
+    if (!coeffs) return set_error(c, TVM_ERR_OUT_OF_MEMORY, "quotient scratch");
+    TVM_TRY(remainder_coset_coefficients(c, mt, at, td, qd, d_ch, d_w, false, coeffs));
     TVM_TRY(tvm_evaluate(c, 3, coeffs, 4 * N, qd, d_out));
     return all_quotients_combined(c, mt->data, mt->layout, (u64)mt->W, at->data, (u64)at->W, N, td.generator, qd.offset, qd.generator,
                                   qd.length, d_ch, d_w, d_out, 1 << 0, 1);
 }
 }  // namespace tvm
 
-int32_t tvm_all_quotients_combined(tvm_ctx* c, const tvm_table* mt, const tvm_table* at, tvm_domain td,
-                                              tvm_domain qd, const uint64_t* h_challenges, const uint64_t* h_weights,
-                                              uint64_t* d_out) {
+// what tvm_all_quotients_combined and tvm_all_quotients_coefficients share: the checks of their arguments, the staging of the
+// challenges and weights, and (below) the gates of valid-trace mode
+static int quotient_arguments(tvm_ctx* c, const tvm_table* mt, const tvm_table* at, tvm_domain td, tvm_domain qd, const uint64_t* h_challenges,
+                              const uint64_t* h_weights, const uint64_t* d_out) {
     if (!c || !mt || !at || !h_challenges || !h_weights || !d_out || !valid_domain(td) || !valid_domain(qd))
         return set_error(c, TVM_ERR_INVALID_ARGUMENT, "all_quotients_combined arguments");
     if (mt->fk != 1 || mt->n_cols != TVM_NUM_MAIN_COLUMNS || at->fk != 3 || at->n_cols != TVM_NUM_AUX_COLUMNS ||
         mt->rows != at->rows || qd.length > mt->rows || !mt->has_successor_blocks || !at->has_successor_blocks ||
         mt->layout.X != at->layout.X || mt->layout.n1 != at->layout.n1 || mt->layout.n2 != at->layout.n2 || mt->layout.pitch != at->layout.pitch)
         return set_error(c, TVM_ERR_INVALID_ARGUMENT, "all_quotients_combined: tables must be 379 BFE / 91 XFE columns wide, made by tvm_lde_table over one domain");
+    return TVM_OK;
+}
+static int stage_quotient_inputs(tvm_ctx* c, const uint64_t* h_challenges, const uint64_t* h_weights, const u64** d_ch, const u64** d_w) {
     u64* staged = (u64*)scratch(c, 13, (size_t)3 * (TVM_NUM_CHALLENGES + TVM_NUM_QUOTIENT_WEIGHTS) * sizeof(u64));
     if (!staged) return set_error(c, TVM_ERR_OUT_OF_MEMORY, "challenge staging");
     TVM_TRY(tvm::h2d_small(c, staged, h_challenges, 3 * TVM_NUM_CHALLENGES * sizeof(u64)));
     TVM_TRY(tvm::h2d_small(c, staged + 3 * TVM_NUM_CHALLENGES, h_weights, 3 * TVM_NUM_QUOTIENT_WEIGHTS * sizeof(u64)));
-    const u64* d_ch = staged;
-    const u64* d_w = staged + 3 * TVM_NUM_CHALLENGES;
+    *d_ch = staged;
+    *d_w = staged + 3 * TVM_NUM_CHALLENGES;
+    return TVM_OK;
+}
+struct QuotientSplit {
+    bool split, split4, split3, remainder;   // the gates in tvm_all_quotients_combined, where each is explained
+};
+static QuotientSplit quotient_split(const tvm_ctx* c, const tvm_table* mt, const tvm_table* at, tvm_domain td, tvm_domain qd);
+
+int32_t tvm_all_quotients_combined(tvm_ctx* c, const tvm_table* mt, const tvm_table* at, tvm_domain td,
+                                              tvm_domain qd, const uint64_t* h_challenges, const uint64_t* h_weights,
+                                              uint64_t* d_out) {
+    TVM_TRY(quotient_arguments(c, mt, at, td, qd, h_challenges, h_weights, d_out));
+    const u64 *d_ch = nullptr, *d_w = nullptr;
+    TVM_TRY(stage_quotient_inputs(c, h_challenges, h_weights, &d_ch, &d_w));
     // Valid-trace mode (tvm_ctx_set_option TVM_OPTION_AIR_VALID_TRACE; off by default).  Every column is a polynomial with at most m = interpolant_len coefficients, every constraint has degree
     // <= 4 in the columns (the AIR is degree-lowered to 4), so a constraint polynomial has degree <= 4(m - 1).  The
     // consistency and transition quotients divide by X^N - 1 (the transition one times X - w^-1): fewer than
@@ -1139,30 +1203,21 @@ int32_t tvm_all_quotients_combined(tvm_ctx* c, const tvm_table* mt, const tvm_ta
     // The constraints of lower degree have shorter quotients still (air_gen.h: TVM_AIR_PART_CLASS): those of class 2 -- a quarter
     // of the multiplications -- have fewer than N + 2h coefficients and are evaluated on a QUARTER of the points, interpolated
     // there, and their coefficients added to the half-domain interpolant before the one evaluation on all points.
-    const u64 m = mt->interpolant_len > at->interpolant_len ? mt->interpolant_len : at->interpolant_len;
-    const u64 half = qd.length / 2, quarter = qd.length / 4;
     // (a quotient domain short enough for the parts to run side by side is evaluated row by row: air.hip, fork lanes)
-    const bool split = c->air_valid_trace && !tvm::air_parts_fork(c, qd.length) && mt->interpolant_len && at->interpolant_len && half >= 2 * td.length && half % td.length == 0 &&
-                       4 * (m - 1) + 2 <= half + td.length && 3 * (m - 1) <= half && mt->rows % half == 0;
-    if (!split)
+    const u64 half = qd.length / 2, quarter = qd.length / 4;
+    const QuotientSplit gate = quotient_split(c, mt, at, td, qd);
+    const bool split4 = gate.split4, split3 = gate.split3;
+    if (!gate.split)
         return all_quotients_combined(c, mt->data, mt->layout, (u64)mt->W, at->data, (u64)at->W, td.length, td.generator,
                                       qd.offset, qd.generator, qd.length, d_ch, d_w, d_out);
     // (class 2 on the quarter domain: transition quotients of degree-2 constraints have 2(m - 1) + 2 - N coefficients at most;
     // class 3 on THREE cosets of the trace domain: those of degree-3 constraints have 3(m - 1) + 2 - N <= 3N)
     const u64 N = td.length;
-    const bool split4 = quarter >= 2 * N && quarter % N == 0 && 2 * (m - 1) + 2 <= quarter + N && m <= quarter;
-    const bool split3 = split4 && half == 4 * N && 3 * (m - 1) + 2 <= 4 * N && 2 * (m - 1) <= 3 * N && mt->layout.X == at->layout.X &&
-                        mt->layout.pitch == at->layout.pitch && mt->layout.X == 2 * (half / N) && mt->layout.pitch % TVM_RB == 0;
     // One coset fewer per class, plus one block T of a sixth coset (quotients_by_remainder_coset, above): when every class's quotient
     // has at most M = n1 coefficients beyond its whole blocks of N -- class 1 (parts 1-5) fewer than 3N + 4h, class 3 (6, 7) 2N + 3h,
     // class 2 (8, 9) N + 2h -- and the trace is long enough that the dropped cosets (about 1.9 ms of AIR work at 2^18 rows, a quarter of
     // that at 2^16) outweigh the latency of the three short evaluations on T (about 0.1 ms each, whatever N).
-    const u64 M = mt->layout.n1;
-    if (split3 && c->air_remainder_coset && N >= c->air_remainder_min_rows && M % TVM_RB == 0 &&
-        4 * (m - 1) + 2 <= 4 * N + M && 3 * (m - 1) <= 3 * N + M &&     // class 1
-        3 * (m - 1) + 2 <= 3 * N + M && 2 * (m - 1) <= 2 * N + M &&     // class 3
-        2 * (m - 1) + 2 <= 2 * N + M && m <= N + M)                     // class 2
-        return tvm::quotients_by_remainder_coset(c, mt, at, td, qd, d_ch, d_w, d_out);
+    if (gate.remainder) return tvm::quotients_by_remainder_coset(c, mt, at, td, qd, d_ch, d_w, d_out);
     PoolBlock low_block(c, (size_t)(2 * 3 * half + (split4 ? 2 * 3 * quarter : 0) + (split3 ? 6 * 3 * N : 0)) * sizeof(u64));  // released on every exit path
     u64* low = (u64*)low_block.p;
     if (!low) return set_error(c, TVM_ERR_OUT_OF_MEMORY, "quotient scratch");
@@ -1238,6 +1293,42 @@ int32_t tvm_all_quotients_combined(tvm_ctx* c, const tvm_table* mt, const tvm_ta
     return rc;
 }
 
+static QuotientSplit quotient_split(const tvm_ctx* c, const tvm_table* mt, const tvm_table* at, tvm_domain td, tvm_domain qd) {
+    const u64 m = mt->interpolant_len > at->interpolant_len ? mt->interpolant_len : at->interpolant_len;
+    const u64 half = qd.length / 2, quarter = qd.length / 4, N = td.length, M = mt->layout.n1;
+    QuotientSplit g;
+    g.split = c->air_valid_trace && !tvm::air_parts_fork(c, qd.length) && mt->interpolant_len && at->interpolant_len && half >= 2 * N && half % N == 0 &&
+              4 * (m - 1) + 2 <= half + N && 3 * (m - 1) <= half && mt->rows % half == 0;
+    g.split4 = g.split && quarter >= 2 * N && quarter % N == 0 && 2 * (m - 1) + 2 <= quarter + N && m <= quarter;
+    g.split3 = g.split4 && half == 4 * N && 3 * (m - 1) + 2 <= 4 * N && 2 * (m - 1) <= 3 * N && mt->layout.X == at->layout.X &&
+               mt->layout.pitch == at->layout.pitch && mt->layout.X == 2 * (half / N) && mt->layout.pitch % TVM_RB == 0;
+    g.remainder = g.split3 && c->air_remainder_coset && N >= c->air_remainder_min_rows && M % TVM_RB == 0 &&
+                  4 * (m - 1) + 1 <= 4 * N + M &&                                 // class 0 (the coefficient form only)
+                  4 * (m - 1) + 2 <= 4 * N + M && 3 * (m - 1) <= 3 * N + M &&     // class 1
+                  3 * (m - 1) + 2 <= 3 * N + M && 2 * (m - 1) <= 2 * N + M &&     // class 3
+                  2 * (m - 1) + 2 <= 2 * N + M && m <= N + M;                     // class 2
+    return g;
+}
+
+// The combined quotient in COEFFICIENT form, for a prover that goes on to the segments (tvm_quotient_segments_from_coefficients): no
+// codeword of the quotient domain is made and taken apart again.  Only where the remainder-coset gate above holds; elsewhere the
+// status is TVM_NOT_APPLICABLE, nothing is written and the caller takes tvm_all_quotients_combined.
+extern "C" int32_t tvm_all_quotients_coefficients(tvm_ctx* c, const tvm_table* mt, const tvm_table* at, tvm_domain td, tvm_domain qd,
+                                                  const uint64_t* h_challenges, const uint64_t* h_weights, uint64_t* d_coeffs,
+                                                  uint64_t capacity, uint64_t* n_coeffs) {
+    if (!n_coeffs) return set_error(c, TVM_ERR_INVALID_ARGUMENT, "all_quotients_coefficients arguments");
+    *n_coeffs = 0;
+    TVM_TRY(quotient_arguments(c, mt, at, td, qd, h_challenges, h_weights, d_coeffs));
+    if (!quotient_split(c, mt, at, td, qd).remainder) return TVM_NOT_APPLICABLE;
+    const u64 n = 4 * td.length + mt->layout.n1;
+    if (capacity < n) return set_error(c, TVM_ERR_INVALID_ARGUMENT, "all_quotients_coefficients: capacity below 4 N + n1 elements");
+    const u64 *d_ch = nullptr, *d_w = nullptr;
+    TVM_TRY(stage_quotient_inputs(c, h_challenges, h_weights, &d_ch, &d_w));
+    TVM_TRY(tvm::remainder_coset_coefficients(c, mt, at, td, qd, d_ch, d_w, true, d_coeffs));
+    *n_coeffs = n;
+    return TVM_OK;
+}
+
 // ---- the valid-trace AIR piecewise: what tvm_all_quotients_combined does in one call on one device, as the pieces a multi-GPU
 // host distributes over its ranks (triton_vm_amd/host/sharded_host.cpp).  A class's quotient polynomial has fewer than n * N
 // coefficients (n = tvm_air_class_cosets), so its values on ANY n cosets of the trace domain determine it.
@@ -1306,7 +1397,7 @@ int32_t tvm_coset_values_to_coefficients(tvm_ctx* c, tvm_domain td, uint32_t n_c
         TVM_TRY(tvm_interpolate(c, 3, d_values[j], dom, q + (u64)j * 3 * N));
         ptrs.q[j] = q + (u64)j * 3 * N;
     }
-    TVM_LAUNCH(tvm::k_coset_combine, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, c->stream, ptrs, (int)n_cosets, N, w, d_coeffs);
+    TVM_LAUNCH(tvm::k_coset_combine, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, c->stream, ptrs, (int)n_cosets, N, w, d_coeffs, 1);
     TVM_HIP_CHECK(c, hipGetLastError());
     return TVM_OK;
 }

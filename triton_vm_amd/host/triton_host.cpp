@@ -594,18 +594,30 @@ ProofStream Prover::prove() {
     ps.enqueue("aux root", merkle_root(c_, aux_nodes).data(), 5);
     const std::vector<Xfe> quotient_weights = xfe_powers(ps.sample_scalars(1)[0], 0, TVM_NUM_QUOTIENT_WEIGHTS);
 
-    // 10: quotient codeword, segments, randomization  (stark.rs:405-423)
+    // 10: quotient, segments, randomization  (stark.rs:405-423).  The quotient codeword is not part of the proof: where the AIR
+    // arrives at the quotient's coefficients (valid-trace mode on a long trace) the segments are taken from them, and only
+    // elsewhere (exact mode, short traces, other expansion factors) a codeword is made and interpolated.
     DeviceBuffer quot(c_, p_.quotient.length * 3);
     if (assume_valid_trace) c_.check(tvm_ctx_set_option(c_.raw(), TVM_OPTION_AIR_VALID_TRACE, 1), "tvm_ctx_set_option");
-    const int32_t quotient_status = tvm_all_quotients_combined(c_.raw(), main_.table(), aux_.table(), p_.trace.c(), p_.quotient.c(),
-                                                               challenges[0].c, quotient_weights[0].c, quot.ptr());
+    u64 n_coeffs = 0;
+    int32_t quotient_status = tvm_all_quotients_coefficients(c_.raw(), main_.table(), aux_.table(), p_.trace.c(), p_.quotient.c(),
+                                                             challenges[0].c, quotient_weights[0].c, quot.ptr(), p_.quotient.length, &n_coeffs);
+    const bool from_coefficients = quotient_status == TVM_OK;
+    if (quotient_status == TVM_NOT_APPLICABLE)
+        quotient_status = tvm_all_quotients_combined(c_.raw(), main_.table(), aux_.table(), p_.trace.c(), p_.quotient.c(), challenges[0].c,
+                                                     quotient_weights[0].c, quot.ptr());
     if (assume_valid_trace) (void)tvm_ctx_set_option(c_.raw(), TVM_OPTION_AIR_VALID_TRACE, 0);
-    c_.check(quotient_status, "tvm_all_quotients_combined");
+    c_.check(quotient_status, from_coefficients ? "tvm_all_quotients_coefficients" : "tvm_all_quotients_combined");
     const u64 poly_len = std::max<u64>(p_.quotient.length / 4, quotient_randomizer_.size());
     DeviceBuffer polys(c_, 5 * poly_len * 3);
     tvm_table* seg_table = nullptr;
-    c_.check(tvm_quotient_segments(c_.raw(), quot.ptr(), p_.quotient.c(), p_.ldt.c(), quotient_randomizer_.data()->c,
-                                   quotient_randomizer_.size(), zeta, &seg_table, polys.ptr(), poly_len), "tvm_quotient_segments");
+    if (from_coefficients)
+        c_.check(tvm_quotient_segments_from_coefficients(c_.raw(), quot.ptr(), n_coeffs, p_.ldt.c(), quotient_randomizer_.data()->c,
+                                                         quotient_randomizer_.size(), zeta, &seg_table, polys.ptr(), poly_len),
+                 "tvm_quotient_segments_from_coefficients");
+    else
+        c_.check(tvm_quotient_segments(c_.raw(), quot.ptr(), p_.quotient.c(), p_.ldt.c(), quotient_randomizer_.data()->c,
+                                       quotient_randomizer_.size(), zeta, &seg_table, polys.ptr(), poly_len), "tvm_quotient_segments");
     struct TableGuard {
         const Context& c;
         tvm_table* t;

@@ -27,6 +27,24 @@ def all_quotients_combined(ctx, main_table, aux_table, trace_domain, quotient_do
     return out
 
 
+NOT_APPLICABLE = 5  # TVM_NOT_APPLICABLE
+
+
+def all_quotients_coefficients(ctx, main_table, aux_table, trace_domain, quotient_domain, challenges, weights, capacity=None):
+    """tvm_all_quotients_coefficients: the combined quotient in coefficient form -> (DeviceBuffer of `capacity` XFE, the number of
+    coefficients written), or None where the entry point does not apply (the caller takes all_quotients_combined)."""
+    ch, w = _h(challenges).reshape(63, 3), _h(weights).reshape(604, 3)
+    capacity = quotient_domain.length if capacity is None else capacity
+    out = ctx.alloc(capacity * 3)
+    n = C.c_uint64(0)
+    status = ctx.lib.tvm_all_quotients_coefficients(ctx.handle, main_table._need_table(), aux_table._need_table(), trace_domain.c(),
+                                                    quotient_domain.c(), ch.ctypes.data, w.ctypes.data, out.ptr, capacity, C.byref(n))
+    if status == NOT_APPLICABLE:
+        return None
+    ctx._check(status, "all_quotients_coefficients")
+    return out, int(n.value)
+
+
 class QuotientSegments:
     """Result of compute_quotient_segments' tail + randomize_quotient_segments (stark.rs:784-792,1302-1356)."""
 
@@ -74,6 +92,16 @@ def quotient_segments(ctx, d_quotient_codeword, quotient_domain, ldt_domain, ran
     ctx._check(ctx.lib.tvm_quotient_segments(ctx.handle, d_quotient_codeword.ptr, quotient_domain.c(), ldt_domain.c(),
                                              rnd.ctypes.data, rnd.shape[0], ZETA, C.byref(t), polys.ptr, poly_len),
                "quotient_segments")
+    return QuotientSegments(ctx, t.value, polys, poly_len, ldt_domain.length)
+
+
+def quotient_segments_from_coefficients(ctx, d_coeffs, n_coeffs, ldt_domain, randomizer, poly_len):
+    rnd = _h(randomizer).reshape(-1, 3)
+    polys = ctx.alloc(5 * poly_len * 3)
+    t = C.c_void_p()
+    ctx._check(ctx.lib.tvm_quotient_segments_from_coefficients(ctx.handle, d_coeffs.ptr, n_coeffs, ldt_domain.c(), rnd.ctypes.data,
+                                                               rnd.shape[0], ZETA, C.byref(t), polys.ptr, poly_len),
+               "quotient_segments_from_coefficients")
     return QuotientSegments(ctx, t.value, polys, poly_len, ldt_domain.length)
 
 
