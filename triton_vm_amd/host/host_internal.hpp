@@ -1,6 +1,8 @@
-// host_internal.hpp -- helpers shared by the translation units of the C++ host (triton_host.cpp, sharded_host.cpp).
-// Not part of the interface: triton_host.hpp is.
+// host_internal.hpp -- what the translation units of the C++ host share (triton_host.cpp, sharded_host.cpp, verifier.cpp): helpers,
+// the steps of one proof (ProofSteps), the frame of an extern "C" entry point.  Not part of the interface: triton_host.hpp is.
 #pragma once
+#include <cstdio>
+#include <cstring>
 #include <string>
 #include <vector>
 
@@ -36,6 +38,7 @@ struct GatherBatch {
         return jobs.size() - 1;
     }
     void run(const Context& c) {
+        if (jobs.empty()) return;
         std::vector<const uint64_t*> src, idx;
         std::vector<uint32_t> words;
         std::vector<uint64_t> n;
@@ -53,5 +56,112 @@ struct GatherBatch {
     }
 };
 
+typedef std::vector<u64> Words;
+
+struct TableGuard {
+    const Context& c;
+    tvm_table* t = nullptr;
+    ~TableGuard() { if (t) tvm_table_free(c.raw(), t); }
+};
+
+// One proof.  prove() is the statement sequence of Prover::prove (stark.rs:331-719) and fri() that of Fri::prove (fri.rs:212-319),
+// each written once (triton_host.cpp); the virtual steps are the ones that depend on where the data lies -- whole on one GPU
+// (Prover, triton_host.cpp) or by cosets over ranks and passes (ShardedRun, sharded_host.cpp).  The hooks of
+// triton_vm_amd/prover.py are the model.  A step's default is the single-GPU one where that is a line.
+class ProofSteps {
+public:
+    enum Which { MAIN = 0, AUX = 1, QUOT = 2 };
+    ProofSteps(const Context& c_, const StarkParameters& p_, const Claim& claim_, MasterTable& main_, MasterTable& aux_,
+               const std::vector<Xfe>& quotient_randomizer_, const std::function<void(const std::vector<Xfe>&)>& extend_,
+               const bool& assume_valid_trace_)
+        : c(c_), p(p_), claim(claim_), main(main_), aux(aux_), quotient_randomizer(quotient_randomizer_), extend(extend_),
+          assume_valid_trace(assume_valid_trace_) {}
+    virtual ~ProofSteps() {}
+    ProofStream prove();
+
+protected:
+    struct Openings {   // of the three tables, by Which
+        Words rows[3], auth[3];
+    };
+    struct FriRound {
+        ArithmeticDomain dom;
+        const u64* cw = nullptr;   // the whole codeword; of a distributed round, this rank's elements
+        DeviceBuffer nodes;        // the whole tree [2 n][5]; none: the round is distributed, answer_distributed knows its tree
+    };
+    struct FriQuery {
+        size_t round;
+        std::vector<u64> indices;
+    };
+    struct FriAnswer {
+        Words leaves, auth;
+    };
+    const Context& c;
+    const StarkParameters& p;
+    const Claim& claim;
+    MasterTable &main, &aux;
+    const std::vector<Xfe>& quotient_randomizer;
+    const std::function<void(const std::vector<Xfe>&)>& extend;
+    const bool& assume_valid_trace;   // (a reference: a checked proof decides while `extend` runs)
+    ProofStream ps;
+    MasterTable& master(Which w) { return w == MAIN ? main : aux; }
+
+    virtual void mark(const char* /*stage*/) {}
+    // this rank's rows of a domain, and the rows of all ranks in row order (w words per row)
+    virtual ArithmeticDomain local(const ArithmeticDomain& d) const { return d; }
+    virtual DeviceBuffer gather_rows(DeviceBuffer&& rows, u64 /*n_local*/, uint32_t /*w*/, const char* /*what*/) { return std::move(rows); }
+    // 4, 8: low-degree extend a master table; 5, 9, 12: commit to it (QUOT: to the segment table) -> the root
+    virtual void extend_master_table(Which w) = 0;
+    virtual Words commit(Which w, const tvm_table* segments) = 0;
+    // 10: the quotient -> the segment table on this rank's LDT rows (the caller frees it) and the five segment polynomials
+    virtual tvm_table* quotient_segments(const std::vector<Xfe>& challenges, const std::vector<Xfe>& weights, u64 zeta, DeviceBuffer& polys,
+                                         u64 poly_len) = 0;
+    virtual Words out_of_domain_rows(const MasterTable& mt, const std::vector<Xfe>& points) { return mt.out_of_domain_rows(points); }
+    // 15: the weighted sums wp, wr of the segments on this rank's rows of the short domain: rows of the segment table
+    virtual void segment_combinations(const tvm_table* segments, const DeviceBuffer& polys, u64 poly_len, const ArithmeticDomain& short_rank,
+                                      const Xfe* wp, const Xfe* wr, DeviceBuffer& cw_p, DeviceBuffer& cw_r);
+    // FRI: the rounds whose tree is split over the ranks (roots enqueued, challenges sampled, folds done), appended to `rounds`;
+    // `dom` moves on to the first round that is not.  -> that round's codeword in row order (after the last round: the last codeword)
+    virtual DeviceBuffer fri_distributed_rounds(DeviceBuffer&& codeword, std::vector<FriRound>& /*rounds*/, ArithmeticDomain& /*dom*/) {
+        return std::move(codeword);
+    }
+    virtual std::vector<FriAnswer> answer_distributed(const std::vector<FriQuery>& /*queries*/) { return {}; }
+    // 19: the rows of the three tables at `indices` and the authentication structures of the three trees
+    virtual Openings open(const tvm_table* segments, const std::vector<u64>& indices) = 0;
+
+private:
+    std::vector<u64> fri(DeviceBuffer&& combination);   // -> the first-round indices
+};
+
+// ---- what every extern "C" entry point does around its body ------------------------------------------------------------
+template <class F>
+int32_t guarded(char* error, uint64_t error_capacity, F body) {
+    try {
+        body();
+        return TVM_OK;
+    } catch (const Error& e) {
+        if (error && error_capacity) std::snprintf(error, error_capacity, "%s", e.what());
+        return e.status ? e.status : TVM_ERR_INVALID_ARGUMENT;
+    } catch (const std::exception& e) {
+        if (error && error_capacity) std::snprintf(error, error_capacity, "%s", e.what());
+        return TVM_ERR_DEVICE;
+    }
+}
+inline Claim make_claim(const u64* h_program_digest, const u64* h_public_input, u64 n_public_input, const u64* h_public_output,
+                        u64 n_public_output) {
+    Claim claim;
+    if (h_program_digest) std::memcpy(claim.program_digest, h_program_digest, sizeof(claim.program_digest));
+    if (n_public_input) claim.input.assign(h_public_input, h_public_input + n_public_input);
+    if (n_public_output) claim.output.assign(h_public_output, h_public_output + n_public_output);
+    return claim;
+}
+inline void copy_proof_out(const Words& proof, u64* h_proof, u64 capacity, u64* proof_words) {
+    if (proof_words) *proof_words = proof.size();
+    if (h_proof && capacity >= proof.size()) std::memcpy(h_proof, proof.data(), proof.size() * sizeof(u64));
+}
+// use_stir: 0 = LdtChoice::Fri, 1 = LdtChoice::Stir, 2 = Stark::ldt's rule (STIR from 2^16 padded rows on, stark.rs:1944-1951)
+inline bool chooses_stir(uint32_t use_stir, uint32_t log2_padded_height, const char* entry) {
+    if (use_stir > 2) throw Error(TVM_ERR_INVALID_ARGUMENT, std::string(entry) + ": use_stir is 0 (FRI), 1 (STIR) or 2 (automatic)");
+    return use_stir == 2 ? log2_padded_height >= 16 : use_stir == 1;
+}
 
 }  // namespace triton_vm

@@ -44,9 +44,8 @@ ShardedProver::ShardedProver(const Context& c, const StarkParameters& p, const t
     if (comm && comm->rank >= comm->world) throw Error(TVM_ERR_INVALID_ARGUMENT, "communicator rank");
 }
 
-typedef std::vector<u64> Words;
-
-struct ShardedRun {
+// One prove(): the steps of ProofSteps (host_internal.hpp) on this rank's cosets
+struct ShardedRun : ProofSteps {
     struct Tree {  // a Merkle tree over n_leaves leaves: whole on this rank, or its lowest levels split over the ranks
         u64 n_leaves = 0;
         DeviceBuffer nodes;  // whole: [2 n][5] heap order; split: the subtree over this rank's contiguous leaf range, [2 n / R][5]
@@ -54,23 +53,16 @@ struct ShardedRun {
         Words top;           // split: the tree over the R subtree roots, [2 R][5], on every rank
         Words root() const { return Words(top.begin() + 5, top.begin() + 10); }
     };
-    struct TableGuard {
-        const Context& c;
-        tvm_table* t = nullptr;
-        ~TableGuard() { if (t) tvm_table_free(c.raw(), t); }
-    };
 
     ShardedProver& sp;
-    const Context& c;
-    const StarkParameters& p;
     const tvmh_comm* comm;
     const u64 R, me, P;
-    ProofStream ps;
     std::chrono::steady_clock::time_point t_stage;
     std::string stage;
 
     explicit ShardedRun(ShardedProver& s)
-        : sp(s), c(s.c_), p(s.p_), comm(s.comm_), R(s.comm_ ? s.comm_->world : 1), me(s.comm_ ? s.comm_->rank : 0), P(s.passes_) {}
+        : ProofSteps(s.c_, s.p_, s.claim_, s.main_, s.aux_, s.quotient_randomizer_, s.extend, s.assume_valid_trace), sp(s), comm(s.comm_),
+          R(s.comm_ ? s.comm_->world : 1), me(s.comm_ ? s.comm_->rank : 0), P(s.passes_) {}
 
     // ---------------------------------------------------------------------------------------------- bookkeeping
     void close_stage() {
@@ -81,7 +73,7 @@ struct ShardedRun {
             if (e.first == stage) { e.second += ms; return; }
         sp.stage_ms.push_back({stage, ms});
     }
-    void mark(const char* name) {
+    void mark(const char* name) override {
         close_stage();
         if (comm && comm->mark) comm->mark(comm->self, c.raw(), name);
         stage = name;
@@ -101,10 +93,10 @@ struct ShardedRun {
 
     // ---------------------------------------------------------------------------------------------- collectives
     // this rank's rows (global row i = local row i / R of rank i % R), n_local elements of w words -> all rows in row order
-    DeviceBuffer gather_rows(DeviceBuffer&& local, u64 n_local, uint32_t w, const char* what) {
-        if (!comm) return std::move(local);
+    DeviceBuffer gather_rows(DeviceBuffer&& rows, u64 n_local, uint32_t w, const char* what) override {
+        if (!comm) return std::move(rows);
         DeviceBuffer all(c, n_local * w * R), out(c, n_local * w * R);
-        comm_check(comm->all_gather(comm->self, c.raw(), local.ptr(), all.ptr(), n_local * w), what);
+        comm_check(comm->all_gather(comm->self, c.raw(), rows.ptr(), all.ptr(), n_local * w), what);
         count(what, n_local * w * 8 * (R - 1));
         for (u64 r = 0; r < R; r++) scatter(all.ptr() + r * n_local * w, w, n_local, R, r, out.ptr());
         return out;
@@ -293,13 +285,17 @@ struct ShardedRun {
     // ---------------------------------------------------------------------------------------------- master tables
     ArithmeticDomain group(const ArithmeticDomain& d, u64 pass) const { return coset_group(d, me + R * pass, R * P); }
 
-    // hash_all_ldt_domain_rows + merkle_tree (master_table.rs:443-503) -> the tree over all L rows
-    Tree commit_master_table(MasterTable& mt, const char* what) {
+    // hash_all_ldt_domain_rows + merkle_tree (master_table.rs:443-503) -> the tree over all L rows, of a master table or (QUOT) of
+    // the segment table, which holds this rank's rows whatever the pass count
+    Tree trees[3];
+    Words commit(Which w, const tvm_table* segments) override {
+        static const char* const what[3] = {"main leaf digests", "aux leaf digests", "quotient leaf digests"};
         const u64 L = p.ldt.length, local_rows = L / R, pass_rows = local_rows / P;
         DeviceBuffer digests(c, 5 * local_rows);
-        if (P == 1) {
-            c.check(tvm_hash_rows(c.raw(), mt.table(), local_rows, digests.ptr()), "tvm_hash_rows");
+        if (w == QUOT || P == 1) {
+            c.check(tvm_hash_rows(c.raw(), w == QUOT ? segments : master(w).table(), local_rows, digests.ptr()), "tvm_hash_rows");
         } else {
+            MasterTable& mt = master(w);
             DeviceBuffer part(c, 5 * pass_rows);
             for (u64 s = 0; s < P; s++) {  // nothing is cached: extend, hash, drop (master_table.rs:470-503)
                 const ArithmeticDomain g = group(p.ldt, s);
@@ -310,7 +306,8 @@ struct ShardedRun {
             }
             mt.clear_cache();
         }
-        return tree_from_local(std::move(digests), L, false, what);
+        trees[w] = tree_from_local(std::move(digests), L, false, what[w]);
+        return trees[w].root();
     }
 
     // The valid-trace AIR over the ranks.  On a valid trace the constraint quotients are polynomials of known
@@ -429,7 +426,7 @@ struct ShardedRun {
 
     // out_of_domain_row at several indeterminates (master_table.rs:348-390), the columns split evenly over the ranks (the
     // traces are replicated) -> [n_points][n_cols][3]
-    Words out_of_domain_rows(const MasterTable& mt, const std::vector<Xfe>& points) {
+    Words out_of_domain_rows(const MasterTable& mt, const std::vector<Xfe>& points) override {
         if (!comm) return mt.out_of_domain_rows(points);
         const u64 n_cols = mt.n_cols(), per = (n_cols + R - 1) / R, n_pts = points.size();
         const u64 c0 = std::min(me * per, n_cols), c1 = std::min(c0 + per, n_cols);
@@ -474,337 +471,129 @@ struct ShardedRun {
     // the residue-r elements of the next codeword -- split_and_fold on the rank's domain (o w^r, w^R, n/R), whose square
     // is the rank's domain of the next round.  The tree of a round needs contiguous leaf ranges: one all-to-all per round.
     // From the first round whose tree is built whole, the codeword is gathered once and the commit phase continues with
-    // the sponge on the device (tvm_fri_commit_phase), replicated.
-    std::vector<u64> fri(DeviceBuffer&& combination_local) {
-        struct Round {
-            ArithmeticDomain dom;
-            const u64* cw = nullptr;  // distributed: this rank's elements; else the whole codeword
-            bool distributed = false;
-            Tree tree;
-        };
-        std::vector<Round> rounds;
-        std::vector<DeviceBuffer> owned;
+    // the sponge on the device (ProofSteps::fri), replicated.
+    struct SplitRound {
+        const u64* cw;   // this rank's elements of the round's codeword
+        Tree tree;
+    };
+    std::vector<SplitRound> split_rounds;
+    std::vector<DeviceBuffer> split_codewords;
+
+    DeviceBuffer fri_distributed_rounds(DeviceBuffer&& combination_local, std::vector<FriRound>& rounds, ArithmeticDomain& dom) override {
+        std::vector<DeviceBuffer>& owned = split_codewords;
         owned.push_back(std::move(combination_local));
-        ArithmeticDomain dom = p.ldt, local_dom = coset_group(p.ldt, me, R);
-        unsigned r = 0;
-        bool folded_past_last = false;
-        for (; r <= p.fri_rounds && splits(dom.length); r++) {
-            Round round;
-            round.dom = dom;
-            round.cw = owned.back().ptr();
-            round.distributed = true;
-            {
-                DeviceBuffer copy(c, 3 * local_dom.length);  // (tree_from_local consumes its argument)
-                c.check(tvm_memcpy_d2d(c.raw(), copy.ptr(), round.cw, 3 * local_dom.length * 8), "tvm_memcpy_d2d");
-                round.tree = tree_from_local(std::move(copy), dom.length, true, "FRI codeword");
-            }
-            ps.enqueue("fri root " + std::to_string(r), round.tree.root().data(), 5);
-            rounds.push_back(std::move(round));
-            if (r == p.fri_rounds) {
-                folded_past_last = true;
-                r++;
-                break;
-            }
+        ArithmeticDomain local_dom = local(p.ldt);
+        for (unsigned r = 0; r <= p.fri_rounds && splits(dom.length); r++) {
+            const u64* cw = owned.back().ptr();
+            DeviceBuffer copy(c, 3 * local_dom.length);  // (tree_from_local consumes its argument)
+            c.check(tvm_memcpy_d2d(c.raw(), copy.ptr(), cw, 3 * local_dom.length * 8), "tvm_memcpy_d2d");
+            split_rounds.push_back(SplitRound{cw, tree_from_local(std::move(copy), dom.length, true, "FRI codeword")});
+            ps.enqueue("fri root " + std::to_string(r), split_rounds.back().tree.root().data(), 5);
+            rounds.push_back(FriRound{dom, cw, DeviceBuffer()});
+            if (r == p.fri_rounds) break;
             const Xfe challenge = ps.sample_scalars(1)[0];
             DeviceBuffer next(c, 3 * (local_dom.length / 2));
-            c.check(tvm_fri_split_and_fold(c.raw(), owned.back().ptr(), local_dom.c(), challenge.c, next.ptr()), "tvm_fri_split_and_fold");
+            c.check(tvm_fri_split_and_fold(c.raw(), cw, local_dom.c(), challenge.c, next.ptr()), "tvm_fri_split_and_fold");
             owned.push_back(std::move(next));
             dom = dom.pow(2);
             local_dom = local_dom.pow(2);
         }
-        // the codeword of round r (or, when every round's tree was split, the last codeword) in row order on every rank
-        const u64* cw;
-        {
-            DeviceBuffer local = std::move(owned.back());
-            owned.pop_back();
-            const bool keep = !rounds.empty() && rounds.back().distributed && rounds.back().cw == local.ptr();
-            if (comm && keep) {  // the last split round still answers queries from the distributed codeword
-                DeviceBuffer copy(c, 3 * local_dom.length);
-                c.check(tvm_memcpy_d2d(c.raw(), copy.ptr(), local.ptr(), 3 * local_dom.length * 8), "tvm_memcpy_d2d");
-                owned.push_back(std::move(local));
-                local = std::move(copy);
-            }
-            owned.push_back(gather_rows(std::move(local), local_dom.length, 3, "FRI codeword (gathered)"));
-            cw = owned.back().ptr();
+        DeviceBuffer mine = std::move(owned.back());
+        owned.pop_back();
+        if (comm && !split_rounds.empty() && split_rounds.back().cw == mine.ptr()) {
+            // every round's tree was split: the last one still answers queries from the distributed codeword
+            DeviceBuffer copy(c, 3 * local_dom.length);
+            c.check(tvm_memcpy_d2d(c.raw(), copy.ptr(), mine.ptr(), 3 * local_dom.length * 8), "tvm_memcpy_d2d");
+            owned.push_back(std::move(mine));
+            mine = std::move(copy);
         }
-        if (!folded_past_last) {
-            const unsigned left = p.fri_rounds - r;  // folds still to do; trees for rounds r .. fri_rounds
-            std::vector<u64*> d_cw, d_nodes;
-            ArithmeticDomain d = dom;
-            const size_t first = rounds.size();
-            for (unsigned k = 0; k <= left; k++) {
-                Round round;
-                round.dom = d;
-                round.tree.n_leaves = d.length;
-                round.tree.nodes = DeviceBuffer(c, 10 * d.length);
-                d_nodes.push_back(round.tree.nodes.ptr());
-                rounds.push_back(std::move(round));
-                if (k == left) break;
-                owned.emplace_back(c, d.length / 2 * 3);
-                d_cw.push_back(owned.back().ptr());
-                d = d.pow(2);
-            }
-            Words roots(5 * (left + 1)), challenges(3 * (size_t)left + 1);
-            c.check(tvm_fri_commit_phase(c.raw(), cw, dom.c(), left, ps.sponge_state(), d_cw.data(), d_nodes.data(), roots.data(),
-                                         challenges.data()), "tvm_fri_commit_phase");
-            for (unsigned k = 0; k <= left; k++) {
-                Round& round = rounds[first + k];
-                round.cw = k == 0 ? cw : d_cw[k - 1];
-                round.tree.top.assign(10, 0);
-                std::copy_n(&roots[5 * k], 5, round.tree.top.begin() + 5);
-                ps.enqueue("fri root " + std::to_string(r + k), &roots[5 * k], 5);
-                if (k == left) break;
-                const Xfe challenge = ps.sample_scalars(1)[0];
-                if (std::memcmp(challenge.c, &challenges[3 * k], 3 * sizeof(u64)) != 0)
-                    throw Error(TVM_ERR_DEVICE, "the device's Fiat-Shamir sponge and the host's disagree on a FRI folding challenge");
-            }
-            cw = rounds.back().cw;
-            dom = rounds.back().dom;
-        }
-        Words last(dom.length * 3);
-        c.check(tvm_memcpy_d2h(c.raw(), last.data(), cw, last.size() * sizeof(u64)), "last codeword");
-        ps.enqueue("fri last codeword", last.data(), last.size());
-        const DeviceBuffer last_poly_d = ArithmeticDomain::of_length(dom.length).interpolate(c, cw, 3);
-        const Words last_poly = last_poly_d.download(0, dom.length * 3);
-        ps.enqueue("fri last polynomial", last_poly.data(), last_poly.size());
-        const std::vector<u64> a_indices = ps.sample_indices(p.ldt.length, p.num_collinearity_checks);
-        // the responses of all rounds in ONE exchange (their order in the proof stream is fixed below)
+        return gather_rows(std::move(mine), local_dom.length, 3, "FRI codeword (gathered)");
+    }
+    // the responses of all distributed rounds in ONE exchange
+    std::vector<FriAnswer> answer_distributed(const std::vector<FriQuery>& queries) override {
         Exchange ex;
-        struct Response {
-            size_t round;
-            bool distributed;
-            size_t leaves_job;
-            Words leaves;
-            AuthJob auth;
-        };
-        std::vector<Response> responses;
-        for (size_t k = 0; k < rounds.size(); k++) {
-            const Round& round = rounds[k];
-            std::vector<u64> b_idx;
-            for (u64 i : a_indices) b_idx.push_back((i % round.dom.length + round.dom.length / 2) % round.dom.length);
-            for (int which = (k == 0 ? 0 : 1); which < 2; which++) {
-                if (which == 1 && k == rounds.size() - 1) continue;
-                const std::vector<u64>& ix = which == 0 ? a_indices : b_idx;
-                auto fetch = [&](const std::vector<u64>& at) {
-                    Words out(at.size() * 3);
-                    c.check(tvm_gather_elements(c.raw(), round.cw, 3, at.data(), at.size(), out.data()), "tvm_gather_elements");
-                    return out;
-                };
-                Response q{k, round.distributed, 0, {}, {}};
-                if (round.distributed) q.leaves_job = add_distributed(ex, ix, 3, fetch);
-                else q.leaves = fetch(ix);
-                q.auth = add_auth(ex, {&round.tree}, ix);
-                responses.push_back(std::move(q));
-            }
+        std::vector<std::pair<size_t, AuthJob>> jobs;
+        for (const FriQuery& q : queries) {
+            const SplitRound& round = split_rounds[q.round];
+            auto fetch = [&](const std::vector<u64>& at) {
+                Words out(at.size() * 3);
+                c.check(tvm_gather_elements(c.raw(), round.cw, 3, at.data(), at.size(), out.data()), "tvm_gather_elements");
+                return out;
+            };
+            const size_t leaves = add_distributed(ex, q.indices, 3, fetch);
+            jobs.push_back({leaves, add_auth(ex, {&round.tree}, q.indices)});
         }
         run(ex, "FRI responses and authentication nodes");
-        for (const Response& q : responses) {
-            const Words& leaves = q.distributed ? ex.jobs[q.leaves_job].out : q.leaves;
-            const Words auth = take_auth(ex, q.auth)[0];
-            ps.enqueue("fri response " + std::to_string(q.round), leaves.data(), leaves.size());
-            ps.enqueue("fri auth " + std::to_string(q.round), auth.data(), auth.size());
-        }
-        (void)ps.sample_scalars(1);
-        return a_indices;
+        std::vector<FriAnswer> answers;
+        for (const auto& job : jobs) answers.push_back(FriAnswer{ex.jobs[job.first].out, take_auth(ex, job.second)[0]});
+        return answers;
     }
 
-    // ---------------------------------------------------------------------------------------------- the proof
-    ProofStream prove() {
-        sp.stage_ms.clear();
-        sp.exchanges.clear();
-        sp.split_trees_built = 0;
-        ps.alter_fiat_shamir_state_with(sp.claim_.encode());  // stark.rs:336-339
-        {
-            const u64 log2_padded_height = to_mont(bit_length(p.padded_height) - 1);  // stark.rs:354
-            ps.enqueue("log2 padded height", &log2_padded_height, 1);
-        }
-        const u64 L = p.ldt.length;
-        const ArithmeticDomain short_dom = p.ldt.length <= p.quotient.length ? p.ldt : p.quotient;
-        const ArithmeticDomain ldt_rank = coset_group(p.ldt, me, R), short_rank = coset_group(short_dom, me, R);
-        const u64 zeta = to_mont(3);  // Stark::ZETA, stark.rs:1801
-        auto enqueue_xfes = [&](const char* name, const std::vector<Xfe>& v) { ps.enqueue(name, v[0].c, 3 * v.size()); };
-        MasterTable &main = sp.main_, &aux = sp.aux_;
+    // ---------------------------------------------------------------------------------------------- the other steps of the proof
+    ArithmeticDomain local(const ArithmeticDomain& d) const override { return coset_group(d, me, R); }
 
-        // 4-6: main table LDE, Merkle tree, challenges  (stark.rs:367-377)
-        // (TVMH_OPTION_COLUMN_SPLIT: the inverse transforms split by columns, the coefficients exchanged -- see extend_table)
-        const unsigned column_chunks = comm && R > 1 && P == 1 ? (unsigned)std::min<u64>(tvmh_get_option(TVMH_OPTION_COLUMN_SPLIT), 16) : 0;
-        auto extend_table = [&](MasterTable& mt, const char* what) {
-            mt.set_domains(ldt_rank, ldt_rank);
-            if (column_chunks) mt.low_degree_extend_over(comm, column_chunks, [&](u64 bytes) { count(what, bytes); });
-            else mt.maybe_low_degree_extend_all_columns();
-        };
-        mark("main LDE");
-        if (P == 1) extend_table(main, "main coefficients");
-        mark("main Merkle");
-        const Tree main_tree = commit_master_table(main, "main leaf digests");
-        ps.enqueue("main root", main_tree.root().data(), 5);
-        const std::vector<Xfe> challenges = derive_challenges(ps.sample_scalars(NUM_SAMPLED_CHALLENGES), sp.claim_);
-        mark("extend");
-        if (sp.extend) sp.extend(challenges);  // MasterMainTable::extend (stark.rs:379-381), replicated
+    // (TVMH_OPTION_COLUMN_SPLIT: the inverse transforms split by columns, the coefficients exchanged -- low_degree_extend_over)
+    void extend_master_table(Which w) override {
+        if (P != 1) return;   // coset-wise passes extend group by group where they hash and open
+        const unsigned column_chunks = comm && R > 1 ? (unsigned)std::min<u64>(tvmh_get_option(TVMH_OPTION_COLUMN_SPLIT), 16) : 0;
+        MasterTable& mt = master(w);
+        mt.set_domains(local(p.ldt), local(p.ldt));
+        if (column_chunks) mt.low_degree_extend_over(comm, column_chunks, [&](u64 bytes) { count(w == MAIN ? "main coefficients" : "aux coefficients", bytes); });
+        else mt.maybe_low_degree_extend_all_columns();
+    }
 
-        // 8-9: aux table
-        mark("aux LDE");
-        if (P == 1) extend_table(aux, "aux coefficients");
-        mark("aux Merkle");
-        const Tree aux_tree = commit_master_table(aux, "aux leaf digests");
-        ps.enqueue("aux root", aux_tree.root().data(), 5);
-        const std::vector<Xfe> quotient_weights = xfe_powers(ps.sample_scalars(1)[0], 0, TVM_NUM_QUOTIENT_WEIGHTS);
-
-        // 10: quotient codeword, segments, randomization  (stark.rs:405-423).  The segment polynomials need the whole
-        // codeword (one interpolation, replicated); the segment TABLE is evaluated on this rank's rows only.
-        mark("AIR quotients");
-        DeviceBuffer quot = quotient_codeword(challenges, quotient_weights);
+    // 10: the segment polynomials need the whole codeword (one interpolation, replicated); the segment TABLE is evaluated on
+    // this rank's rows only.  The quotient is a codeword here: by classes or by groups, not yet in coefficient form.
+    tvm_table* quotient_segments(const std::vector<Xfe>& challenges, const std::vector<Xfe>& weights, u64 zeta, DeviceBuffer& polys,
+                                 u64 poly_len) override {
+        const DeviceBuffer quot = quotient_codeword(challenges, weights);
         mark("quotient segments LDE");
-        const u64 poly_len = std::max<u64>(p.quotient.length / 4, sp.quotient_randomizer_.size());
-        DeviceBuffer polys(c, 5 * poly_len * 3);
-        TableGuard seg{c};
-        c.check(tvm_quotient_segments(c.raw(), quot.ptr(), p.quotient.c(), ldt_rank.c(), sp.quotient_randomizer_.data()->c,
-                                      sp.quotient_randomizer_.size(), zeta, &seg.t, polys.ptr(), poly_len), "tvm_quotient_segments");
-        quot.reset();
-        // 12: quotient Merkle tree  (stark.rs:425-446)
-        mark("quotient Merkle");
-        Tree quot_tree;
-        {
-            DeviceBuffer digests(c, 5 * ldt_rank.length);
-            c.check(tvm_hash_rows(c.raw(), seg.t, ldt_rank.length, digests.ptr()), "tvm_hash_rows");
-            quot_tree = tree_from_local(std::move(digests), L, false, "quotient leaf digests");
-        }
-        ps.enqueue("quot root", quot_tree.root().data(), 5);
+        polys = DeviceBuffer(c, 5 * poly_len * 3);
+        tvm_table* seg = nullptr;
+        c.check(tvm_quotient_segments(c.raw(), quot.ptr(), p.quotient.c(), local(p.ldt).c(), quotient_randomizer.data()->c,
+                                      quotient_randomizer.size(), zeta, &seg, polys.ptr(), poly_len), "tvm_quotient_segments");
+        return seg;
+    }
 
-        // 13: out-of-domain rows  (stark.rs:450-495)
-        mark("out-of-domain rows");
-        const Xfe alpha = ps.sample_scalars(1)[0];
-        const Xfe alpha_next = xfe_scale(alpha, p.trace.generator);
-        const Words ood_main = out_of_domain_rows(main, {alpha, alpha_next});
-        const Words ood_aux = out_of_domain_rows(aux, {alpha, alpha_next});
-        const Xfe a4 = xfe_powers(alpha, 4, 1)[0];
-        const Xfe za4 = xfe_powers(xfe_scale(alpha, zeta), 4, 1)[0];
-        Xfe seg_ood[5][2];
-        {
-            const Xfe pts[2] = {a4, za4};   // the five segment polynomials at both points: one round trip
-            c.check(tvm_evaluate_polys_at_points(c.raw(), polys.ptr(), poly_len, poly_len, 5, pts[0].c, 2, seg_ood[0][0].c),
-                    "tvm_evaluate_polys_at_points");
-        }
-        ps.enqueue("ood main", ood_main.data(), NUM_MAIN * 3);
-        ps.enqueue("ood aux", ood_aux.data(), NUM_AUX * 3);
-        ps.enqueue("ood main next", ood_main.data() + NUM_MAIN * 3, NUM_MAIN * 3);
-        ps.enqueue("ood aux next", ood_aux.data() + NUM_AUX * 3, NUM_AUX * 3);
-        enqueue_xfes("ood quot p", {seg_ood[0][0], seg_ood[1][0], seg_ood[2][0], seg_ood[3][0]});
-        enqueue_xfes("ood quot r", {seg_ood[1][1], seg_ood[2][1], seg_ood[3][1], seg_ood[4][1]});
+    // When the LDT domain is the short one the values of the P and R polynomials (stark.rs:520-540) are row-wise combinations of
+    // the rank's segment table.  When the quotient domain is the short one, its row s is LDT row s |LDT| / |quotient|, which lives
+    // on rank (s |LDT| / |quotient|) mod R -- not on the rank that owns short row s -- so the two polynomials are formed from the
+    // segment polynomials and evaluated on the rank's rows.
+    void segment_combinations(const tvm_table* segments, const DeviceBuffer& polys, u64 poly_len, const ArithmeticDomain& short_rank,
+                              const Xfe* wp, const Xfe* wr, DeviceBuffer& cw_p, DeviceBuffer& cw_r) override {
+        if (short_rank.length * R == p.ldt.length) return ProofSteps::segment_combinations(segments, polys, poly_len, short_rank, wp, wr, cw_p, cw_r);
+        DeviceBuffer poly(c, poly_len * 3);
+        c.check(tvm_xfe_linear_combination(c.raw(), polys.ptr(), 5, poly_len, poly_len, wp->c, poly.ptr()), "tvm_xfe_linear_combination");
+        cw_p = short_rank.evaluate(c, poly.ptr(), poly_len, 3);
+        c.check(tvm_xfe_linear_combination(c.raw(), polys.ptr(), 5, poly_len, poly_len, wr->c, poly.ptr()), "tvm_xfe_linear_combination");
+        cw_r = short_rank.evaluate(c, poly.ptr(), poly_len, 3);
+    }
 
-        // 14-15: combination weights, linear combinations  (stark.rs:497-543), on this rank's rows of the short domain
-        mark("linear combination");
-        const std::vector<Xfe> w3 = ps.sample_scalars(3);
-        const std::vector<Xfe> weights_ma = xfe_powers(w3[0], 0, NUM_MAIN + NUM_AUX);
-        const std::vector<Xfe> weights_q = xfe_powers(w3[1], 0, 5);
-        const std::vector<Xfe> weights_d = xfe_powers(w3[2], 0, 4);
-        DeviceBuffer comb = main.weighted_sum_of_columns(&weights_ma[0]);
-        {
-            const DeviceBuffer comb_aux = aux.weighted_sum_of_columns(&weights_ma[NUM_MAIN]);
-            c.check(tvm_xfe_add_assign(c.raw(), comb.ptr(), comb_aux.ptr(), 2 * p.trace.length), "tvm_xfe_add_assign");
-        }
-        const u64 n_comb = p.trace.length + p.h;
-        const DeviceBuffer main_aux_codeword = short_rank.evaluate(c, comb.ptr(), n_comb, 3);
-        std::vector<Xfe> wp = weights_q, wr = weights_q;
-        wp[4] = Xfe{{0, 0, 0}};
-        wr[0] = Xfe{{0, 0, 0}};
-        // values of the P and R polynomials (stark.rs:520-540) on this rank's rows of the short domain.  When that is the LDT
-        // domain they are row-wise combinations of the rank's segment table.  When the quotient domain is the short one, its
-        // row s is LDT row s |LDT| / |quotient|, which lives on rank (s |LDT| / |quotient|) mod R -- not on the rank that owns
-        // short row s -- so the two polynomials are formed from the segment polynomials and evaluated on the rank's rows.
-        DeviceBuffer cw_p, cw_r;
-        if (short_dom.length == L) {
-            cw_p = DeviceBuffer(c, short_rank.length * 3);
-            cw_r = DeviceBuffer(c, short_rank.length * 3);
-            c.check(tvm_table_linear_combination(c.raw(), seg.t, short_rank.length, wp[0].c, cw_p.ptr()), "tvm_table_linear_combination");
-            c.check(tvm_table_linear_combination(c.raw(), seg.t, short_rank.length, wr[0].c, cw_r.ptr()), "tvm_table_linear_combination");
-        } else {
-            DeviceBuffer poly(c, poly_len * 3);
-            c.check(tvm_xfe_linear_combination(c.raw(), polys.ptr(), 5, poly_len, poly_len, wp[0].c, poly.ptr()), "tvm_xfe_linear_combination");
-            cw_p = short_rank.evaluate(c, poly.ptr(), poly_len, 3);
-            c.check(tvm_xfe_linear_combination(c.raw(), polys.ptr(), 5, poly_len, poly_len, wr[0].c, poly.ptr()), "tvm_xfe_linear_combination");
-            cw_r = short_rank.evaluate(c, poly.ptr(), poly_len, 3);
-        }
-        Xfe ma_values[2];
-        {
-            const Xfe pts[2] = {alpha, alpha_next};
-            c.check(tvm_evaluate_at_points(c.raw(), comb.ptr(), n_comb, pts[0].c, 2, ma_values[0].c), "tvm_evaluate_at_points");
-        }
-        Xfe p_value{{0, 0, 0}}, r_value{{0, 0, 0}};
-        for (int k = 0; k < 4; k++) p_value = xfe_add(p_value, xfe_mul(weights_q[k], seg_ood[k][0]));
-        for (int k = 1; k < 5; k++) r_value = xfe_add(r_value, xfe_mul(weights_q[k], seg_ood[k][1]));
-
-        // 16: DEEP  (stark.rs:545-639), row-local
-        mark("DEEP");
-        DeviceBuffer combination(c, short_rank.length * 3);
-        {
-            const u64* cws[4] = {main_aux_codeword.ptr(), main_aux_codeword.ptr(), cw_p.ptr(), cw_r.ptr()};
-            const Xfe points[4] = {alpha, alpha_next, a4, za4}, values[4] = {ma_values[0], ma_values[1], p_value, r_value};
-            c.check(tvm_deep_codeword(c.raw(), 4, cws, short_rank.c(), points[0].c, values[0].c, weights_d[0].c, combination.ptr()),
-                    "tvm_deep_codeword");
-        }
-        cw_p.reset();
-        cw_r.reset();
-        comb.reset();
-        if (short_dom.length != L) {  // stark.rs:629-639: the quotient domain was the short one -- extend to the LDT domain
-            const DeviceBuffer whole = gather_rows(std::move(combination), short_rank.length, 3, "combination codeword (short domain)");
-            const DeviceBuffer coeffs = p.quotient.interpolate(c, whole.ptr(), 3);
-            combination = ldt_rank.evaluate(c, coeffs.ptr(), p.quotient.length, 3);
-        }
-
-        // 17: the low-degree test  (stark.rs:641-663)
-        mark(p.use_stir ? "STIR" : "FRI");
-        std::vector<u64> a_indices;
-        if (p.use_stir) {  // Stir::prove on the whole codeword, replicated
-            const DeviceBuffer whole = gather_rows(std::move(combination), ldt_rank.length, 3, "combination codeword");
-            a_indices = p.stir.prove(c, whole.ptr(), ps);
-        } else {
-            a_indices = fri(std::move(combination));
-        }
-
-        // 18: the out-of-domain point must not collide with a revealed in-domain point  (stark.rs:645-663)
-        if (a4.c[1] == 0 && a4.c[2] == 0) {
-            const u64 other = mont_mul(a4.c[0], mont_pow(zeta, 4));
-            for (u64 i : a_indices) {
-                const u64 x = p.ldt.value(i);
-                if (x == a4.c[0] || x == other) throw Error(TVM_ERR_INVALID_ARGUMENT, "ZeroKnowledgeViolation (stark.rs:645-663)");
-            }
-        }
-
-        // 19: open the trace leafs  (stark.rs:665-716)
-        mark("open trace leafs");
-        {
-            Exchange ex;   // the rows of the three tables and the authentication nodes of the three trees: one exchange
-            const AuthJob auth_job = add_auth(ex, {&main_tree, &aux_tree, &quot_tree}, a_indices);
-            const size_t main_job = add_master_rows(ex, main, a_indices), aux_job = add_master_rows(ex, aux, a_indices);
-            auto fetch = [&](const std::vector<u64>& local) {
-                Words rows(local.size() * 15);
-                c.check(tvm_table_reveal_rows(c.raw(), seg.t, ldt_rank.length, local.data(), local.size(), rows.data()), "quotient rows");
-                return rows;
-            };
-            const size_t quot_job = add_distributed(ex, a_indices, 15, fetch);
-            run(ex, "opened rows and authentication nodes");
-            const std::vector<Words> auth = take_auth(ex, auth_job);
-            const Words &main_rows = ex.jobs[main_job].out, &aux_rows = ex.jobs[aux_job].out, &qrows = ex.jobs[quot_job].out;
-            ps.enqueue("main rows", main_rows.data(), main_rows.size());
-            ps.enqueue("main auth", auth[0].data(), auth[0].size());
-            ps.enqueue("aux rows", aux_rows.data(), aux_rows.size());
-            ps.enqueue("aux auth", auth[1].data(), auth[1].size());
-            ps.enqueue("quot rows", qrows.data(), qrows.size());
-            ps.enqueue("quot auth", auth[2].data(), auth[2].size());
-        }
-        main.clear_cache();
-        aux.clear_cache();
-        c.check(tvm_sync(c.raw()), "tvm_sync");
-        close_stage();
-        stage.clear();
-        return std::move(ps);
+    // the rows of the three tables and the authentication nodes of the three trees: one exchange
+    Openings open(const tvm_table* segments, const std::vector<u64>& indices) override {
+        Exchange ex;
+        const AuthJob auth_job = add_auth(ex, {&trees[MAIN], &trees[AUX], &trees[QUOT]}, indices);
+        const size_t main_job = add_master_rows(ex, main, indices), aux_job = add_master_rows(ex, aux, indices);
+        auto fetch = [&](const std::vector<u64>& at) {
+            Words rows(at.size() * 15);
+            c.check(tvm_table_reveal_rows(c.raw(), segments, p.ldt.length / R, at.data(), at.size(), rows.data()), "quotient rows");
+            return rows;
+        };
+        const size_t quot_job = add_distributed(ex, indices, 15, fetch);
+        run(ex, "opened rows and authentication nodes");
+        const std::vector<Words> auth = take_auth(ex, auth_job);
+        return Openings{{ex.jobs[main_job].out, ex.jobs[aux_job].out, ex.jobs[quot_job].out}, {auth[MAIN], auth[AUX], auth[QUOT]}};
     }
 };
 
 ProofStream ShardedProver::prove() {
+    stage_ms.clear();
+    exchanges.clear();
+    split_trees_built = 0;
     ShardedRun run(*this);
-    return run.prove();
+    ProofStream stream = run.prove();
+    run.close_stage();
+    return stream;
 }
 
 std::string ShardedProver::stats_json() const {
@@ -1253,23 +1042,6 @@ extern "C" uint64_t tvmh_local_comms_report(const tvmh_comm* any, char* json, ui
     return s.size() + 1;
 }
 
-namespace {
-template <class F>
-int32_t guarded(char* error, uint64_t error_capacity, F body) {
-    using namespace triton_vm;
-    try {
-        body();
-        return TVM_OK;
-    } catch (const Error& e) {
-        if (error && error_capacity) std::snprintf(error, error_capacity, "%s", e.what());
-        return e.status ? e.status : TVM_ERR_INVALID_ARGUMENT;
-    } catch (const std::exception& e) {
-        if (error && error_capacity) std::snprintf(error, error_capacity, "%s", e.what());
-        return TVM_ERR_DEVICE;
-    }
-}
-}  // namespace
-
 extern "C" int32_t tvmh_prove_execution_sharded(tvm_ctx* ctx, const tvmh_comm* comm, uint32_t jit_passes, uint64_t split_tree_min_leaves,
                                                 const tvm_aet* aet, uint32_t log2_padded_height, uint32_t security_level,
                                                 uint32_t log2_expansion, uint32_t use_stir, const uint8_t randomness_seed[32],
@@ -1280,20 +1052,15 @@ extern "C" int32_t tvmh_prove_execution_sharded(tvm_ctx* ctx, const tvmh_comm* c
     using namespace triton_vm;
     return guarded(error, error_capacity, [&] {
         if (!aet || !randomness_seed) throw Error(TVM_ERR_INVALID_ARGUMENT, "tvmh_prove_execution_sharded: null execution trace or seed");
-        if (use_stir > 2) throw Error(TVM_ERR_INVALID_ARGUMENT, "tvmh_prove_execution_sharded: use_stir is 0 (FRI), 1 (STIR) or 2 (automatic)");
+        const bool stir = chooses_stir(use_stir, log2_padded_height, "tvmh_prove_execution_sharded");
         const Context c(ctx);
-        const bool stir = use_stir == 2 ? log2_padded_height >= 16 : use_stir == 1;
         const StarkParameters p = stark_parameters(log2_padded_height, security_level, log2_expansion, stir);
-        Claim claim;
-        if (h_program_digest) std::memcpy(claim.program_digest, h_program_digest, sizeof(claim.program_digest));
-        if (n_public_input) claim.input.assign(h_public_input, h_public_input + n_public_input);
-        if (n_public_output) claim.output.assign(h_public_output, h_public_output + n_public_output);
+        const Claim claim = make_claim(h_program_digest, h_public_input, n_public_input, h_public_output, n_public_output);
         std::string stats;
         const std::vector<u64> proof = prove_execution_sharded(c, p, comm, jit_passes, *aet, claim, randomness_seed, profile != 0, &stats,
                                                                split_tree_min_leaves);
         if (stats_json && stats_capacity) std::snprintf(stats_json, stats_capacity, "%s", stats.c_str());
-        if (proof_words) *proof_words = proof.size();
-        if (h_proof && capacity >= proof.size()) std::memcpy(h_proof, proof.data(), proof.size() * sizeof(u64));
+        copy_proof_out(proof, h_proof, capacity, proof_words);
     });
 }
 
@@ -1321,8 +1088,6 @@ extern "C" int32_t tvmh_prove_sharded(tvm_ctx* ctx, const tvmh_comm* comm, uint3
         const CommSession session(comm, c);
         ShardedProver prover(c, p, comm, jit_passes, d_main_trace, d_main_randomizers, d_aux_trace, d_aux_randomizers, qr);
         prover.split_tree_min_leaves = split_tree_min_leaves;
-        const std::vector<u64> proof = prover.prove().proof();
-        if (proof_words) *proof_words = proof.size();
-        if (h_proof && capacity >= proof.size()) std::memcpy(h_proof, proof.data(), proof.size() * sizeof(u64));
+        copy_proof_out(prover.prove().proof(), h_proof, capacity, proof_words);
     });
 }

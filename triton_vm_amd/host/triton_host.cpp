@@ -117,18 +117,16 @@ const Variant VARIANTS[] = {
     {"StirOutOfDomainValues", 3, true}, {"AuthenticationStructure", 5, false}, {"MasterMainTableRows", 379, false},
     {"MasterAuxTableRows", 273, false}, {"QuotientSegmentsElements", 15, false}, {"FriCodeword", 3, false},
     {"FriResponse", RESPONSE, false}, {"StirResponse", RESPONSE, false}};
-// the labels this prover enqueues under -> proof item
-const struct { const char* prefix; int variant; } LABELS[] = {
-    {"log2 padded height", 1}, {"ood main", 2}, {"ood aux", 3}, {"ood quot", 4}, {"fri last codeword", 11},
-    {"fri last polynomial", 5}, {"fri response", 12}, {"fri auth", 12}, {"main rows", 8}, {"aux rows", 9}, {"quot rows", 10},
-    {"main auth", 7}, {"aux auth", 7}, {"quot auth", 7}, {"main root", 0}, {"aux root", 0}, {"quot root", 0}, {"fri root", 0},
-    {"stir root", 0}, {"stir ood values", 6}, {"stir final polynomial", 5}, {"stir response leafs", 13}, {"stir response auth", 13}};
+// the words of a label this prover enqueues under that name its proof item; the first match counts (the two parts of a
+// response, leaves and authentication structure, before a table's " auth")
+const struct { const char* words; int variant; } LABELS[] = {
+    {" root", 0}, {"height", 1}, {"ood main", 2}, {"ood aux", 3}, {"ood quot", 4}, {"stir ood", 6}, {"codeword", 11}, {"polynomial", 5},
+    {"fri ", 12}, {"stir response", 13}, {"main rows", 8}, {"aux rows", 9}, {"quot rows", 10}, {" auth", 7}};
 int variant_of(const std::string& label) {
     for (const auto& l : LABELS)
-        if (label.compare(0, std::strlen(l.prefix), l.prefix) == 0) return l.variant;
+        if (label.find(l.words) != std::string::npos) return l.variant;
     throw Error(TVM_ERR_INVALID_ARGUMENT, "no proof item for the label " + label);
 }
-typedef std::vector<u64> Words;
 void push_len(Words& v, u64 n) { v.push_back(to_mont(n)); }
 void append(Words& v, const Words& w) { v.insert(v.end(), w.begin(), w.end()); }
 void append_dynamic(Words& v, const Words& w) { push_len(v, w.size()); append(v, w); }
@@ -494,74 +492,80 @@ Prover::Prover(const Context& c, const StarkParameters& p, const u64* d_main_tra
 
 // Fri::prove (fri.rs:212-319, 754-772): commit and fold round by round, send the last codeword and polynomial,
 // answer the queries.  Returns the first-round indices.
-std::vector<u64> Prover::fri(const DeviceBuffer& combination, ProofStream& ps) {
-    struct Round {
-        ArithmeticDomain dom;
-        const u64* cw;
-        DeviceBuffer nodes;
-    };
-    std::vector<Round> rounds;
-    std::vector<DeviceBuffer> folded;  // owns the codewords of rounds 1..
-    ArithmeticDomain dom = p_.ldt;
-    const u64* cw = combination.ptr();
-    {
+std::vector<u64> ProofSteps::fri(DeviceBuffer&& combination) {
+    std::vector<FriRound> rounds;
+    std::vector<DeviceBuffer> owned;  // the codewords from the first whole round on
+    ArithmeticDomain dom = p.ldt;
+    owned.push_back(fri_distributed_rounds(std::move(combination), rounds, dom));
+    const u64* cw = owned.back().ptr();
+    if (rounds.size() <= p.fri_rounds) {
         // The commit phase in one call, the sponge on the device (tvm_fri_commit_phase): trees, roots into the transcript,
         // folding challenges, folds -- then the same enqueues and samplings are replayed on this host's sponge, which must
         // arrive at the same challenges.
+        const unsigned first = (unsigned)rounds.size(), left = p.fri_rounds - first;  // folds still to do; trees for rounds first .. fri_rounds
         std::vector<u64*> d_cw, d_nodes;
         ArithmeticDomain d = dom;
-        for (unsigned r = 0; r <= p_.fri_rounds; r++) {
-            rounds.push_back(Round{d, nullptr, DeviceBuffer(c_, 10 * d.length)});
+        for (unsigned k = 0; k <= left; k++) {
+            rounds.push_back(FriRound{d, nullptr, DeviceBuffer(c, 10 * d.length)});
             d_nodes.push_back(rounds.back().nodes.ptr());
-            if (r == p_.fri_rounds) break;
-            folded.emplace_back(c_, d.length / 2 * 3);
-            d_cw.push_back(folded.back().ptr());
+            if (k == left) break;
+            owned.emplace_back(c, d.length / 2 * 3);
+            d_cw.push_back(owned.back().ptr());
             d = d.pow(2);
         }
-        std::vector<u64> roots(5 * (p_.fri_rounds + 1)), challenges(3 * (size_t)p_.fri_rounds + 1);
-        c_.check(tvm_fri_commit_phase(c_.raw(), cw, dom.c(), p_.fri_rounds, ps.sponge_state(), d_cw.data(), d_nodes.data(), roots.data(),
-                                      challenges.data()), "tvm_fri_commit_phase");
-        for (unsigned r = 0; r <= p_.fri_rounds; r++) {
-            rounds[r].cw = r == 0 ? cw : folded[r - 1].ptr();
-            ps.enqueue("fri root " + std::to_string(r), &roots[5 * r], 5);
-            if (r == p_.fri_rounds) break;
+        std::vector<u64> roots(5 * (left + 1)), challenges(3 * (size_t)left + 1);
+        c.check(tvm_fri_commit_phase(c.raw(), cw, dom.c(), left, ps.sponge_state(), d_cw.data(), d_nodes.data(), roots.data(),
+                                     challenges.data()), "tvm_fri_commit_phase");
+        for (unsigned k = 0; k <= left; k++) {
+            rounds[first + k].cw = k == 0 ? cw : d_cw[k - 1];
+            ps.enqueue("fri root " + std::to_string(first + k), &roots[5 * k], 5);
+            if (k == left) break;
             const Xfe challenge = ps.sample_scalars(1)[0];
-            if (std::memcmp(challenge.c, &challenges[3 * r], 3 * sizeof(u64)) != 0)
+            if (std::memcmp(challenge.c, &challenges[3 * k], 3 * sizeof(u64)) != 0)
                 throw Error(TVM_ERR_DEVICE, "the device's Fiat-Shamir sponge and the host's disagree on a FRI folding challenge");
         }
         cw = rounds.back().cw;
         dom = rounds.back().dom;
     }
     std::vector<u64> last(dom.length * 3);
-    c_.check(tvm_memcpy_d2h(c_.raw(), last.data(), cw, last.size() * sizeof(u64)), "last codeword");
+    c.check(tvm_memcpy_d2h(c.raw(), last.data(), cw, last.size() * sizeof(u64)), "last codeword");
     ps.enqueue("fri last codeword", last.data(), last.size());
-    const DeviceBuffer last_poly_d = ArithmeticDomain::of_length(dom.length).interpolate(c_, cw, 3);
+    const DeviceBuffer last_poly_d = ArithmeticDomain::of_length(dom.length).interpolate(c, cw, 3);
     const std::vector<u64> last_poly = last_poly_d.download(0, dom.length * 3);
     ps.enqueue("fri last polynomial", last_poly.data(), last_poly.size());
-    last_polynomial.resize(dom.length);
-    std::memcpy(last_polynomial.data(), last_poly.data(), last_poly.size() * sizeof(u64));
-    const std::vector<u64> a_indices = ps.sample_indices(p_.ldt.length, p_.num_collinearity_checks);
-    // the responses of all rounds in one round trip to the device (their order in the proof stream is fixed below)
+    const std::vector<u64> a_indices = ps.sample_indices(p.ldt.length, p.num_collinearity_checks);
+    // the responses of all whole rounds in one round trip to the device, those of the distributed rounds in one exchange
+    // (their order in the proof stream is fixed below)
     GatherBatch batch;
+    std::vector<FriQuery> distributed;
     struct Response {
-        size_t round, leaves, auth;
+        size_t round;
+        bool distributed;
+        size_t leaves, auth;   // jobs of the batch; distributed: leaves = the query
     };
     std::vector<Response> responses;
     for (size_t r = 0; r < rounds.size(); r++) {
-        const Round& round = rounds[r];
+        const FriRound& round = rounds[r];
         std::vector<u64> b_idx;
         for (u64 i : a_indices) b_idx.push_back((i % round.dom.length + round.dom.length / 2) % round.dom.length);
         for (int which = (r == 0 ? 0 : 1); which < 2; which++) {
             if (which == 1 && r == rounds.size() - 1) continue;
             const std::vector<u64>& ix = which == 0 ? a_indices : b_idx;
+            if (!round.nodes.ptr()) {
+                distributed.push_back(FriQuery{r, ix});
+                responses.push_back(Response{r, true, distributed.size() - 1, 0});
+                continue;
+            }
             const size_t leaves = batch.add(round.cw, 3, ix);
             const size_t auth = batch.add(round.nodes.ptr(), 5, auth_node_indices(round.dom.length, ix));
-            responses.push_back(Response{r, leaves, auth});
+            responses.push_back(Response{r, false, leaves, auth});
         }
     }
-    batch.run(c_);
+    batch.run(c);
+    const std::vector<FriAnswer> answers = answer_distributed(distributed);
     for (const Response& q : responses) {
-        const std::vector<u64>&leaves = batch.jobs[q.leaves].out, &auth = batch.jobs[q.auth].out;
+        const std::vector<u64>& leaves = q.distributed ? answers[q.leaves].leaves : batch.jobs[q.leaves].out;
+        const std::vector<u64>& auth = q.distributed ? answers[q.leaves].auth : batch.jobs[q.auth].out;
         ps.enqueue("fri response " + std::to_string(q.round), leaves.data(), leaves.size());
         ps.enqueue("fri auth " + std::to_string(q.round), auth.data(), auth.size());
     }
@@ -569,78 +573,65 @@ std::vector<u64> Prover::fri(const DeviceBuffer& combination, ProofStream& ps) {
     return a_indices;
 }
 
-ProofStream Prover::prove() {
-    ProofStream ps;
-    ps.alter_fiat_shamir_state_with(claim_.encode());  // stark.rs:336-339
+void ProofSteps::segment_combinations(const tvm_table* segments, const DeviceBuffer&, u64, const ArithmeticDomain& short_rank, const Xfe* wp,
+                                      const Xfe* wr, DeviceBuffer& cw_p, DeviceBuffer& cw_r) {
+    // the points of the short domain are the rows i * L/|short| of the segment table, which was evaluated on the LDT domain
+    cw_p = DeviceBuffer(c, short_rank.length * 3);
+    cw_r = DeviceBuffer(c, short_rank.length * 3);
+    c.check(tvm_table_linear_combination(c.raw(), segments, short_rank.length, wp->c, cw_p.ptr()), "tvm_table_linear_combination");
+    c.check(tvm_table_linear_combination(c.raw(), segments, short_rank.length, wr->c, cw_r.ptr()), "tvm_table_linear_combination");
+}
+
+ProofStream ProofSteps::prove() {
+    ps.alter_fiat_shamir_state_with(claim.encode());  // stark.rs:336-339
     {
-        const u64 log2_padded_height = to_mont(bit_length(p_.padded_height) - 1);  // stark.rs:354
+        const u64 log2_padded_height = to_mont(bit_length(p.padded_height) - 1);  // stark.rs:354
         ps.enqueue("log2 padded height", &log2_padded_height, 1);
     }
-    const u64 L = p_.ldt.length;
-    const ArithmeticDomain short_dom = p_.ldt.length <= p_.quotient.length ? p_.ldt : p_.quotient;
+    const u64 L = p.ldt.length;
+    const ArithmeticDomain short_dom = p.ldt.length <= p.quotient.length ? p.ldt : p.quotient;
+    const ArithmeticDomain ldt_rank = local(p.ldt), short_rank = local(short_dom);   // (one rank: the domains themselves)
     const u64 zeta = to_mont(3);  // Stark::ZETA, stark.rs:1801
     auto enqueue_xfes = [&](const char* name, const std::vector<Xfe>& v) { ps.enqueue(name, v[0].c, 3 * v.size()); };
 
     // 4-6: main table LDE, Merkle tree, challenges  (stark.rs:367-377)
-    main_.maybe_low_degree_extend_all_columns();
-    const DeviceBuffer main_nodes = main_.merkle_tree();
-    ps.enqueue("main root", merkle_root(c_, main_nodes).data(), 5);
-    const std::vector<Xfe> challenges = derive_challenges(ps.sample_scalars(NUM_SAMPLED_CHALLENGES), claim_);
-    if (extend) extend(challenges);  // MasterMainTable::extend (stark.rs:379-381)
+    mark("main LDE");
+    extend_master_table(MAIN);
+    mark("main Merkle");
+    ps.enqueue("main root", commit(MAIN, nullptr).data(), 5);
+    const std::vector<Xfe> challenges = derive_challenges(ps.sample_scalars(NUM_SAMPLED_CHALLENGES), claim);
+    mark("extend");
+    if (extend) extend(challenges);  // MasterMainTable::extend (stark.rs:379-381); over ranks: replicated
 
     // 8-9: aux table (its `extend` is host work in the reference; the trace is already resident)
-    aux_.maybe_low_degree_extend_all_columns();
-    const DeviceBuffer aux_nodes = aux_.merkle_tree();
-    ps.enqueue("aux root", merkle_root(c_, aux_nodes).data(), 5);
+    mark("aux LDE");
+    extend_master_table(AUX);
+    mark("aux Merkle");
+    ps.enqueue("aux root", commit(AUX, nullptr).data(), 5);
     const std::vector<Xfe> quotient_weights = xfe_powers(ps.sample_scalars(1)[0], 0, TVM_NUM_QUOTIENT_WEIGHTS);
 
-    // 10: quotient, segments, randomization  (stark.rs:405-423).  The quotient codeword is not part of the proof: where the AIR
-    // arrives at the quotient's coefficients (valid-trace mode on a long trace) the segments are taken from them, and only
-    // elsewhere (exact mode, short traces, other expansion factors) a codeword is made and interpolated.
-    DeviceBuffer quot(c_, p_.quotient.length * 3);
-    if (assume_valid_trace) c_.check(tvm_ctx_set_option(c_.raw(), TVM_OPTION_AIR_VALID_TRACE, 1), "tvm_ctx_set_option");
-    u64 n_coeffs = 0;
-    int32_t quotient_status = tvm_all_quotients_coefficients(c_.raw(), main_.table(), aux_.table(), p_.trace.c(), p_.quotient.c(),
-                                                             challenges[0].c, quotient_weights[0].c, quot.ptr(), p_.quotient.length, &n_coeffs);
-    const bool from_coefficients = quotient_status == TVM_OK;
-    if (quotient_status == TVM_NOT_APPLICABLE)
-        quotient_status = tvm_all_quotients_combined(c_.raw(), main_.table(), aux_.table(), p_.trace.c(), p_.quotient.c(), challenges[0].c,
-                                                     quotient_weights[0].c, quot.ptr());
-    if (assume_valid_trace) (void)tvm_ctx_set_option(c_.raw(), TVM_OPTION_AIR_VALID_TRACE, 0);
-    c_.check(quotient_status, from_coefficients ? "tvm_all_quotients_coefficients" : "tvm_all_quotients_combined");
-    const u64 poly_len = std::max<u64>(p_.quotient.length / 4, quotient_randomizer_.size());
-    DeviceBuffer polys(c_, 5 * poly_len * 3);
-    tvm_table* seg_table = nullptr;
-    if (from_coefficients)
-        c_.check(tvm_quotient_segments_from_coefficients(c_.raw(), quot.ptr(), n_coeffs, p_.ldt.c(), quotient_randomizer_.data()->c,
-                                                         quotient_randomizer_.size(), zeta, &seg_table, polys.ptr(), poly_len),
-                 "tvm_quotient_segments_from_coefficients");
-    else
-        c_.check(tvm_quotient_segments(c_.raw(), quot.ptr(), p_.quotient.c(), p_.ldt.c(), quotient_randomizer_.data()->c,
-                                       quotient_randomizer_.size(), zeta, &seg_table, polys.ptr(), poly_len), "tvm_quotient_segments");
-    struct TableGuard {
-        const Context& c;
-        tvm_table* t;
-        ~TableGuard() { tvm_table_free(c.raw(), t); }
-    } seg_guard{c_, seg_table};
-    quot.reset();
+    // 10: quotient, segments, randomization  (stark.rs:405-423).  The quotient codeword is not part of the proof.
+    mark("AIR quotients");
+    const u64 poly_len = std::max<u64>(p.quotient.length / 4, quotient_randomizer.size());
+    DeviceBuffer polys;
+    const TableGuard seg{c, quotient_segments(challenges, quotient_weights, zeta, polys, poly_len)};
     // 12: quotient Merkle tree  (stark.rs:425-446)
-    DeviceBuffer quot_nodes(c_, 10 * L);
-    c_.check(tvm_table_merkle_tree(c_.raw(), seg_table, L, quot_nodes.ptr()), "quotient merkle tree");
-    ps.enqueue("quot root", merkle_root(c_, quot_nodes).data(), 5);
+    mark("quotient Merkle");
+    ps.enqueue("quot root", commit(QUOT, seg.t).data(), 5);
 
     // 13: out-of-domain rows  (stark.rs:450-495)
+    mark("out-of-domain rows");
     const Xfe alpha = ps.sample_scalars(1)[0];
-    const Xfe alpha_next = xfe_scale(alpha, p_.trace.generator);
-    const std::vector<u64> ood_main = main_.out_of_domain_rows({alpha, alpha_next});
-    const std::vector<u64> ood_aux = aux_.out_of_domain_rows({alpha, alpha_next});
+    const Xfe alpha_next = xfe_scale(alpha, p.trace.generator);
+    const std::vector<u64> ood_main = out_of_domain_rows(main, {alpha, alpha_next});
+    const std::vector<u64> ood_aux = out_of_domain_rows(aux, {alpha, alpha_next});
     const Xfe a4 = xfe_powers(alpha, 4, 1)[0];
     const Xfe za4 = xfe_powers(xfe_scale(alpha, zeta), 4, 1)[0];
     Xfe seg_ood[5][2];
     {
         const Xfe pts[2] = {a4, za4};   // the five segment polynomials at both points: one round trip
-        c_.check(tvm_evaluate_polys_at_points(c_.raw(), polys.ptr(), poly_len, poly_len, 5, pts[0].c, 2, seg_ood[0][0].c),
-                 "tvm_evaluate_polys_at_points");
+        c.check(tvm_evaluate_polys_at_points(c.raw(), polys.ptr(), poly_len, poly_len, 5, pts[0].c, 2, seg_ood[0][0].c),
+                "tvm_evaluate_polys_at_points");
     }
     ps.enqueue("ood main", ood_main.data(), NUM_MAIN * 3);
     ps.enqueue("ood aux", ood_aux.data(), NUM_AUX * 3);
@@ -649,86 +640,144 @@ ProofStream Prover::prove() {
     enqueue_xfes("ood quot p", {seg_ood[0][0], seg_ood[1][0], seg_ood[2][0], seg_ood[3][0]});
     enqueue_xfes("ood quot r", {seg_ood[1][1], seg_ood[2][1], seg_ood[3][1], seg_ood[4][1]});
 
-    // 14-15: combination weights, linear combinations  (stark.rs:497-543)
+    // 14-15: combination weights, linear combinations  (stark.rs:497-543), on this rank's rows of the short domain
+    mark("linear combination");
     const std::vector<Xfe> w3 = ps.sample_scalars(3);
     const std::vector<Xfe> weights_ma = xfe_powers(w3[0], 0, NUM_MAIN + NUM_AUX);
     const std::vector<Xfe> weights_q = xfe_powers(w3[1], 0, 5);
     const std::vector<Xfe> weights_d = xfe_powers(w3[2], 0, 4);
-    DeviceBuffer comb = main_.weighted_sum_of_columns(&weights_ma[0]);
+    DeviceBuffer comb = main.weighted_sum_of_columns(&weights_ma[0]);
     {
-        const DeviceBuffer comb_aux = aux_.weighted_sum_of_columns(&weights_ma[NUM_MAIN]);
-        c_.check(tvm_xfe_add_assign(c_.raw(), comb.ptr(), comb_aux.ptr(), 2 * p_.trace.length), "tvm_xfe_add_assign");
+        const DeviceBuffer comb_aux = aux.weighted_sum_of_columns(&weights_ma[NUM_MAIN]);
+        c.check(tvm_xfe_add_assign(c.raw(), comb.ptr(), comb_aux.ptr(), 2 * p.trace.length), "tvm_xfe_add_assign");
     }
-    const u64 n_comb = p_.trace.length + p_.h;
-    const DeviceBuffer main_aux_codeword = short_dom.evaluate(c_, comb.ptr(), n_comb, 3);
+    const u64 n_comb = p.trace.length + p.h;
+    const DeviceBuffer main_aux_codeword = short_rank.evaluate(c, comb.ptr(), n_comb, 3);
     std::vector<Xfe> wp = weights_q, wr = weights_q;
     wp[4] = Xfe{{0, 0, 0}};
     wr[0] = Xfe{{0, 0, 0}};
-    // values of the P and R polynomials on the short domain (stark.rs:536-539): its points are the rows i * L/|short| of
-    // the segment table, which was evaluated on the LDT domain
-    DeviceBuffer cw_p(c_, short_dom.length * 3), cw_r(c_, short_dom.length * 3);
-    c_.check(tvm_table_linear_combination(c_.raw(), seg_table, short_dom.length, wp[0].c, cw_p.ptr()), "tvm_table_linear_combination");
-    c_.check(tvm_table_linear_combination(c_.raw(), seg_table, short_dom.length, wr[0].c, cw_r.ptr()), "tvm_table_linear_combination");
+    DeviceBuffer cw_p, cw_r;   // values of the P and R polynomials on the short domain (stark.rs:520-540)
+    segment_combinations(seg.t, polys, poly_len, short_rank, &wp[0], &wr[0], cw_p, cw_r);
     Xfe ma_values[2];
     {
         const Xfe pts[2] = {alpha, alpha_next};
-        c_.check(tvm_evaluate_at_points(c_.raw(), comb.ptr(), n_comb, pts[0].c, 2, ma_values[0].c), "tvm_evaluate_at_points");
+        c.check(tvm_evaluate_at_points(c.raw(), comb.ptr(), n_comb, pts[0].c, 2, ma_values[0].c), "tvm_evaluate_at_points");
     }
     Xfe p_value{{0, 0, 0}}, r_value{{0, 0, 0}};
     for (int k = 0; k < 4; k++) p_value = xfe_add(p_value, xfe_mul(weights_q[k], seg_ood[k][0]));
     for (int k = 1; k < 5; k++) r_value = xfe_add(r_value, xfe_mul(weights_q[k], seg_ood[k][1]));
 
-    // 16: DEEP  (stark.rs:545-639)
-    DeviceBuffer combination(c_, short_dom.length * 3);
+    // 16: DEEP  (stark.rs:545-639), row-local
+    mark("DEEP");
+    DeviceBuffer combination(c, short_rank.length * 3);
     {
         const u64* cws[4] = {main_aux_codeword.ptr(), main_aux_codeword.ptr(), cw_p.ptr(), cw_r.ptr()};
         const Xfe points[4] = {alpha, alpha_next, a4, za4}, values[4] = {ma_values[0], ma_values[1], p_value, r_value};
-        c_.check(tvm_deep_codeword(c_.raw(), 4, cws, short_dom.c(), points[0].c, values[0].c, weights_d[0].c, combination.ptr()),
-                 "tvm_deep_codeword");
+        c.check(tvm_deep_codeword(c.raw(), 4, cws, short_rank.c(), points[0].c, values[0].c, weights_d[0].c, combination.ptr()),
+                "tvm_deep_codeword");
     }
     cw_p.reset();
     cw_r.reset();
     comb.reset();
     if (short_dom.length != L) {  // stark.rs:629-639: the quotient domain was the short one -- extend to the LDT domain
-        const DeviceBuffer coeffs = p_.quotient.interpolate(c_, combination.ptr(), 3);
-        combination = p_.ldt.evaluate(c_, coeffs.ptr(), p_.quotient.length, 3);
+        const DeviceBuffer whole = gather_rows(std::move(combination), short_rank.length, 3, "combination codeword (short domain)");
+        const DeviceBuffer coeffs = p.quotient.interpolate(c, whole.ptr(), 3);
+        combination = ldt_rank.evaluate(c, coeffs.ptr(), p.quotient.length, 3);
     }
 
-    // 17: the low-degree test  (stark.rs:641-663)
-    const std::vector<u64> a_indices = p_.use_stir ? p_.stir.prove(c_, combination.ptr(), ps) : fri(combination, ps);
+    // 17: the low-degree test  (stark.rs:641-663); Stir::prove on the whole codeword, over ranks: replicated
+    mark(p.use_stir ? "STIR" : "FRI");
+    std::vector<u64> a_indices;
+    if (p.use_stir) {
+        const DeviceBuffer whole = gather_rows(std::move(combination), ldt_rank.length, 3, "combination codeword");
+        a_indices = p.stir.prove(c, whole.ptr(), ps);
+    } else {
+        a_indices = fri(std::move(combination));
+    }
 
     // 18: the out-of-domain point must not collide with a revealed in-domain point  (stark.rs:645-663)
     if (a4.c[1] == 0 && a4.c[2] == 0) {
         const u64 other = mont_mul(a4.c[0], mont_pow(zeta, 4));
         for (u64 i : a_indices) {
-            const u64 x = p_.ldt.value(i);
+            const u64 x = p.ldt.value(i);
             if (x == a4.c[0] || x == other) throw Error(TVM_ERR_INVALID_ARGUMENT, "ZeroKnowledgeViolation (stark.rs:645-663)");
         }
     }
 
-    // 19: open the trace leafs  (stark.rs:665-716): the three trees have the same shape and the same revealed leaves, hence
-    // the same authentication-structure node indices; their nodes come back in one round trip
+    // 19: open the trace leafs  (stark.rs:665-716)
+    mark("open trace leafs");
     {
-        const std::vector<u64> auth_idx = auth_node_indices(L, a_indices);
-        GatherBatch batch;
-        const size_t a_main = batch.add(main_nodes.ptr(), 5, auth_idx), a_aux = batch.add(aux_nodes.ptr(), 5, auth_idx),
-                     a_quot = batch.add(quot_nodes.ptr(), 5, auth_idx);
-        batch.run(c_);
-        const std::vector<u64> main_rows = main_.reveal_rows(a_indices), aux_rows = aux_.reveal_rows(a_indices);
-        std::vector<u64> qrows(a_indices.size() * 15);
-        c_.check(tvm_table_reveal_rows(c_.raw(), seg_table, L, a_indices.data(), a_indices.size(), qrows.data()), "quotient rows");
-        ps.enqueue("main rows", main_rows.data(), main_rows.size());
-        ps.enqueue("main auth", batch.jobs[a_main].out.data(), batch.jobs[a_main].out.size());
-        ps.enqueue("aux rows", aux_rows.data(), aux_rows.size());
-        ps.enqueue("aux auth", batch.jobs[a_aux].out.data(), batch.jobs[a_aux].out.size());
-        ps.enqueue("quot rows", qrows.data(), qrows.size());
-        ps.enqueue("quot auth", batch.jobs[a_quot].out.data(), batch.jobs[a_quot].out.size());
+        const Openings o = open(seg.t, a_indices);
+        ps.enqueue("main rows", o.rows[MAIN].data(), o.rows[MAIN].size());
+        ps.enqueue("main auth", o.auth[MAIN].data(), o.auth[MAIN].size());
+        ps.enqueue("aux rows", o.rows[AUX].data(), o.rows[AUX].size());
+        ps.enqueue("aux auth", o.auth[AUX].data(), o.auth[AUX].size());
+        ps.enqueue("quot rows", o.rows[QUOT].data(), o.rows[QUOT].size());
+        ps.enqueue("quot auth", o.auth[QUOT].data(), o.auth[QUOT].size());
     }
-    main_.clear_cache();
-    aux_.clear_cache();
-    c_.check(tvm_sync(c_.raw()), "tvm_sync");
-    return ps;
+    main.clear_cache();
+    aux.clear_cache();
+    c.check(tvm_sync(c.raw()), "tvm_sync");
+    return std::move(ps);
 }
+
+namespace {
+// The whole tables on one GPU: cached extensions, whole trees, the quotient in coefficient form where the AIR yields it.
+struct WholeSteps : ProofSteps {
+    using ProofSteps::ProofSteps;
+    DeviceBuffer nodes[3];   // the three Merkle trees, by Which
+
+    void extend_master_table(Which w) override { master(w).maybe_low_degree_extend_all_columns(); }
+    Words commit(Which w, const tvm_table* segments) override {
+        nodes[w] = DeviceBuffer(c, 10 * p.ldt.length);
+        c.check(tvm_table_merkle_tree(c.raw(), w == QUOT ? segments : master(w).table(), p.ldt.length, nodes[w].ptr()), "tvm_table_merkle_tree");
+        return merkle_root(c, nodes[w]);
+    }
+    // Where the AIR arrives at the quotient's coefficients (valid-trace mode on a long trace) the segments are taken from them, and
+    // only elsewhere (exact mode, short traces, other expansion factors) a codeword is made and interpolated.
+    tvm_table* quotient_segments(const std::vector<Xfe>& challenges, const std::vector<Xfe>& weights, u64 zeta, DeviceBuffer& polys,
+                                 u64 poly_len) override {
+        DeviceBuffer quot(c, p.quotient.length * 3);
+        if (assume_valid_trace) c.check(tvm_ctx_set_option(c.raw(), TVM_OPTION_AIR_VALID_TRACE, 1), "tvm_ctx_set_option");
+        u64 n_coeffs = 0;
+        int32_t status = tvm_all_quotients_coefficients(c.raw(), main.table(), aux.table(), p.trace.c(), p.quotient.c(), challenges[0].c,
+                                                        weights[0].c, quot.ptr(), p.quotient.length, &n_coeffs);
+        const bool from_coefficients = status == TVM_OK;
+        if (status == TVM_NOT_APPLICABLE)
+            status = tvm_all_quotients_combined(c.raw(), main.table(), aux.table(), p.trace.c(), p.quotient.c(), challenges[0].c, weights[0].c,
+                                                quot.ptr());
+        if (assume_valid_trace) (void)tvm_ctx_set_option(c.raw(), TVM_OPTION_AIR_VALID_TRACE, 0);
+        c.check(status, from_coefficients ? "tvm_all_quotients_coefficients" : "tvm_all_quotients_combined");
+        polys = DeviceBuffer(c, 5 * poly_len * 3);
+        tvm_table* seg = nullptr;
+        if (from_coefficients)
+            c.check(tvm_quotient_segments_from_coefficients(c.raw(), quot.ptr(), n_coeffs, p.ldt.c(), quotient_randomizer.data()->c,
+                                                            quotient_randomizer.size(), zeta, &seg, polys.ptr(), poly_len),
+                    "tvm_quotient_segments_from_coefficients");
+        else
+            c.check(tvm_quotient_segments(c.raw(), quot.ptr(), p.quotient.c(), p.ldt.c(), quotient_randomizer.data()->c,
+                                          quotient_randomizer.size(), zeta, &seg, polys.ptr(), poly_len), "tvm_quotient_segments");
+        return seg;
+    }
+    // the three trees have the same shape and the same revealed leaves, hence the same authentication-structure node indices;
+    // their nodes come back in one round trip
+    Openings open(const tvm_table* segments, const std::vector<u64>& indices) override {
+        const std::vector<u64> auth_idx = auth_node_indices(p.ldt.length, indices);
+        GatherBatch batch;
+        for (const DeviceBuffer& tree : nodes) batch.add(tree.ptr(), 5, auth_idx);
+        batch.run(c);
+        Openings o;
+        o.rows[MAIN] = main.reveal_rows(indices);
+        o.rows[AUX] = aux.reveal_rows(indices);
+        o.rows[QUOT].resize(indices.size() * 15);
+        c.check(tvm_table_reveal_rows(c.raw(), segments, p.ldt.length, indices.data(), indices.size(), o.rows[QUOT].data()), "quotient rows");
+        for (int w = 0; w < 3; w++) o.auth[w] = std::move(batch.jobs[w].out);
+        return o;
+    }
+};
+}  // namespace
+
+ProofStream Prover::prove() { return WholeSteps(c_, p_, claim_, main_, aux_, quotient_randomizer_, extend, assume_valid_trace).prove(); }
 
 // ------------------------------------------------------------------------------------------------ STIR
 namespace {
@@ -988,13 +1037,11 @@ DeviceBuffer upload(const Context& c, const std::vector<u64>& host) {
 
 ExecutionTables::ExecutionTables(const Context& c, const StarkParameters& p, const tvm_aet& aet, const uint8_t seed[32],
                                  const std::function<void(const char*)>& lap) {
-    const u64 n = p.trace.length;
     // the seeded randomness: offsets as in the table of master_table.rs:618-628.  The 470 trace-randomizer streams are drawn on the
     // device, one launch per table (tvm_stdrng_streams; round 6: they were 1.3 ms of sequential ChaCha on a helper thread, hidden
     // behind fill + pad at 2^20 rows and the largest idle gap of a proof of a short trace)
-    uint8_t aux_seed[32], batch_seed[32], quotient_seed[32];
+    uint8_t aux_seed[32], quotient_seed[32];
     offset_rng_seed(seed, NUM_MAIN, aux_seed);
-    offset_rng_seed(aux_seed, NUM_AUX, batch_seed);
     offset_rng_seed(seed, NUM_MAIN + NUM_AUX + 1, quotient_seed);
     quotient_randomizer.resize(p.num_quotient_randomizers);
     if (!quotient_randomizer.empty()) tvm_host_stdrng_elements(quotient_seed, 3 * quotient_randomizer.size(), quotient_randomizer.data()->c);
@@ -1003,17 +1050,25 @@ ExecutionTables::ExecutionTables(const Context& c, const StarkParameters& p, con
     c.check(tvm_stdrng_streams(c.raw(), seed, NUM_MAIN, p.h, main_rnd.ptr()), "tvm_stdrng_streams");
     c.check(tvm_stdrng_streams(c.raw(), aux_seed, NUM_AUX, 3 * p.h, aux_rnd.ptr()), "tvm_stdrng_streams");
     lap("trace randomizers");
+    fill_trace(c, p.trace.length, p.padded_height, aet, seed, lap);
+}
+
+void ExecutionTables::fill_trace(const Context& c, u64 n, u64 padded_height, const tvm_aet& aet, const uint8_t seed[32],
+                                 const std::function<void(const char*)>& lap) {
     // MasterMainTable::new + pad (master_table.rs:881-983)
     main_trace = DeviceBuffer(c, NUM_MAIN * n);
     u64 lengths[9];
     c.check(tvm_fill_main_table(c.raw(), &aet, main_trace.ptr(), n, lengths), "tvm_fill_main_table");
     for (u64 len : lengths)
-        if (len > p.padded_height) throw Error(TVM_ERR_INVALID_ARGUMENT, "a table is longer than the padded height");
+        if (len > padded_height) throw Error(TVM_ERR_INVALID_ARGUMENT, "a table is longer than the padded height");
     lap("fill from the AET");
     c.check(tvm_pad_main_table(c.raw(), main_trace.ptr(), n, lengths), "tvm_pad_main_table");
     c.check(tvm_fill_derived_main_columns(c.raw(), main_trace.ptr(), n), "tvm_fill_derived_main_columns");
     lap("pad + derived main columns");
     // MasterMainTable::extend (master_table.rs:1006-1075): the batch-randomizer column now, the rest once the challenges exist
+    uint8_t aux_seed[32], batch_seed[32];
+    offset_rng_seed(seed, NUM_MAIN, aux_seed);
+    offset_rng_seed(aux_seed, NUM_AUX, batch_seed);
     aux_trace = DeviceBuffer(c, NUM_AUX * n * 3);
     c.check(tvm_stdrng_elements(c.raw(), batch_seed, 3 * n, aux_trace.ptr() + (NUM_AUX - 1) * n * 3), "tvm_stdrng_elements");
     lap("batch randomizer column");
@@ -1082,28 +1137,16 @@ extern "C" int32_t tvmh_prove(tvm_ctx* ctx, uint32_t log2_padded_height, uint64_
                               const uint64_t* h_public_output, uint64_t n_public_output, uint32_t use_stir, uint64_t* h_proof,
                               uint64_t capacity, uint64_t* proof_words, char* error, uint64_t error_capacity) {
     using namespace triton_vm;
-    try {
+    return guarded(error, error_capacity, [&] {
         const Context c(ctx);
         const StarkParameters p = use_stir ? stark_parameters(log2_padded_height, 160, log2_expansion, true)
                                            : StarkParameters(log2_padded_height, num_trace_randomizers, num_collinearity_checks, log2_expansion);
         std::vector<Xfe> qr(p.num_quotient_randomizers);
         std::memcpy(qr.data(), h_quotient_randomizer, qr.size() * sizeof(Xfe));
-        Claim claim;
-        if (h_program_digest) std::memcpy(claim.program_digest, h_program_digest, sizeof(claim.program_digest));
-        if (n_public_input) claim.input.assign(h_public_input, h_public_input + n_public_input);
-        if (n_public_output) claim.output.assign(h_public_output, h_public_output + n_public_output);
-        Prover prover(c, p, d_main_trace, d_main_randomizers, d_aux_trace, d_aux_randomizers, qr, claim);
-        const std::vector<u64> proof = prover.prove().proof();
-        if (proof_words) *proof_words = proof.size();
-        if (h_proof && capacity >= proof.size()) std::memcpy(h_proof, proof.data(), proof.size() * sizeof(u64));
-        return TVM_OK;
-    } catch (const Error& e) {
-        if (error && error_capacity) std::snprintf(error, error_capacity, "%s", e.what());
-        return e.status ? e.status : TVM_ERR_INVALID_ARGUMENT;
-    } catch (const std::exception& e) {
-        if (error && error_capacity) std::snprintf(error, error_capacity, "%s", e.what());
-        return TVM_ERR_DEVICE;
-    }
+        Prover prover(c, p, d_main_trace, d_main_randomizers, d_aux_trace, d_aux_randomizers, qr,
+                      make_claim(h_program_digest, h_public_input, n_public_input, h_public_output, n_public_output));
+        copy_proof_out(prover.prove().proof(), h_proof, capacity, proof_words);
+    });
 }
 
 extern "C" int32_t tvmh_prove_execution(tvm_ctx* ctx, const tvm_aet* aet, uint32_t log2_padded_height, uint32_t security_level,
@@ -1113,17 +1156,12 @@ extern "C" int32_t tvmh_prove_execution(tvm_ctx* ctx, const tvm_aet* aet, uint32
                                         uint64_t* h_proof, uint64_t capacity, uint64_t* proof_words, char* error,
                                         uint64_t error_capacity) {
     using namespace triton_vm;
-    try {
+    return guarded(error, error_capacity, [&] {
         if (!aet || !randomness_seed) throw Error(TVM_ERR_INVALID_ARGUMENT, "tvmh_prove_execution: null execution trace or seed");
         const Context c(ctx);
-        // use_stir: 0 = LdtChoice::Fri, 1 = LdtChoice::Stir, 2 = Stark::ldt's rule (STIR from 2^16 padded rows on, stark.rs:1944-1951)
-        if (use_stir > 2) throw Error(TVM_ERR_INVALID_ARGUMENT, "tvmh_prove_execution: use_stir is 0 (FRI), 1 (STIR) or 2 (automatic)");
-        const bool stir = use_stir == 2 ? log2_padded_height >= 16 : use_stir == 1;
+        const bool stir = chooses_stir(use_stir, log2_padded_height, "tvmh_prove_execution");
         const StarkParameters p = stark_parameters(log2_padded_height, security_level, log2_expansion, stir);
-        Claim claim;
-        if (h_program_digest) std::memcpy(claim.program_digest, h_program_digest, sizeof(claim.program_digest));
-        if (n_public_input) claim.input.assign(h_public_input, h_public_input + n_public_input);
-        if (n_public_output) claim.output.assign(h_public_output, h_public_output + n_public_output);
+        const Claim claim = make_claim(h_program_digest, h_public_input, n_public_input, h_public_output, n_public_output);
         // The reference's memory policy (master_table.rs:268-271, stark.rs:730-768): the cached extension first; when the device (or
         // the context's memory limit) cannot hold it, the same proof coset by coset with as few passes as fit (sharded_host.cpp).
         std::vector<u64> proof;
@@ -1139,16 +1177,8 @@ extern "C" int32_t tvmh_prove_execution(tvm_ctx* ctx, const tvm_aet* aet, uint32
             // the policy of the sharded entry from two passes on (sharded_host.cpp: pass counts by estimate, retries on out-of-memory)
             proof = prove_execution_sharded(c, p, nullptr, 0, *aet, claim, randomness_seed, false, nullptr, 1ull << 21, 2);
         }
-        if (proof_words) *proof_words = proof.size();
-        if (h_proof && capacity >= proof.size()) std::memcpy(h_proof, proof.data(), proof.size() * sizeof(u64));
-        return TVM_OK;
-    } catch (const Error& e) {
-        if (error && error_capacity) std::snprintf(error, error_capacity, "%s", e.what());
-        return e.status ? e.status : TVM_ERR_INVALID_ARGUMENT;
-    } catch (const std::exception& e) {
-        if (error && error_capacity) std::snprintf(error, error_capacity, "%s", e.what());
-        return TVM_ERR_DEVICE;
-    }
+        copy_proof_out(proof, h_proof, capacity, proof_words);
+    });
 }
 
 extern "C" int32_t tvmh_check_execution(tvm_ctx* ctx, const tvm_aet* aet, uint32_t log2_padded_height, const uint8_t seed[32],
@@ -1156,46 +1186,27 @@ extern "C" int32_t tvmh_check_execution(tvm_ctx* ctx, const tvm_aet* aet, uint32
                                         const uint64_t* h_public_output, uint64_t n_public_output, uint64_t capacity, uint64_t* h_failures,
                                         uint64_t* n_failures, uint64_t* failing_rows, char* error, uint64_t error_capacity) {
     using namespace triton_vm;
-    try {
+    return guarded(error, error_capacity, [&] {
         if (!aet || !seed || !n_failures || !failing_rows || (capacity && !h_failures) || log2_padded_height < 1 || log2_padded_height > 40)
             throw Error(TVM_ERR_INVALID_ARGUMENT, "tvmh_check_execution: arguments");
         const Context c(ctx);
         const u64 n = 1ull << log2_padded_height;
-        Claim claim;
-        if (h_program_digest) std::memcpy(claim.program_digest, h_program_digest, sizeof(claim.program_digest));
-        if (n_public_input) claim.input.assign(h_public_input, h_public_input + n_public_input);
-        if (n_public_output) claim.output.assign(h_public_output, h_public_output + n_public_output);
-        // the trace prove_execution would prove (ExecutionTables without the trace randomizers): fill, pad, derived columns, the
-        // batch-randomizer column, extend -- with 59 challenges drawn from `seed` and the 4 the claim derives
-        DeviceBuffer main_trace(c, NUM_MAIN * n), aux_trace(c, NUM_AUX * n * 3);
-        u64 lengths[9];
-        c.check(tvm_fill_main_table(c.raw(), aet, main_trace.ptr(), n, lengths), "tvm_fill_main_table");
-        for (u64 len : lengths)
-            if (len > n) throw Error(TVM_ERR_INVALID_ARGUMENT, "a table is longer than the padded height");
-        c.check(tvm_pad_main_table(c.raw(), main_trace.ptr(), n, lengths), "tvm_pad_main_table");
-        c.check(tvm_fill_derived_main_columns(c.raw(), main_trace.ptr(), n), "tvm_fill_derived_main_columns");
-        uint8_t aux_seed[32], batch_seed[32], weight_seed[32];
-        offset_rng_seed(seed, NUM_MAIN, aux_seed);
-        offset_rng_seed(aux_seed, NUM_AUX, batch_seed);
+        const Claim claim = make_claim(h_program_digest, h_public_input, n_public_input, h_public_output, n_public_output);
+        // the trace prove_execution would prove (ExecutionTables without the trace randomizers), extended with 59 challenges drawn
+        // from `seed` and the 4 the claim derives
+        ExecutionTables t;
+        t.fill_trace(c, n, n, *aet, seed, [](const char*) {});
+        uint8_t weight_seed[32];
         offset_rng_seed(seed, NUM_MAIN + NUM_AUX + 2, weight_seed);
-        c.check(tvm_stdrng_elements(c.raw(), batch_seed, 3 * n, aux_trace.ptr() + (NUM_AUX - 1) * n * 3), "tvm_stdrng_elements");
         std::vector<Xfe> sampled(NUM_SAMPLED_CHALLENGES);
         tvm_host_stdrng_elements(seed, 3 * sampled.size(), sampled[0].c);
         const std::vector<Xfe> challenges = derive_challenges(sampled, claim);
-        c.check(tvm_extend_aux_table(c.raw(), main_trace.ptr(), aux_trace.ptr(), n, challenges[0].c), "tvm_extend_aux_table");
-        c.check(tvm_fill_derived_aux_columns(c.raw(), main_trace.ptr(), aux_trace.ptr(), n, challenges[0].c), "tvm_fill_derived_aux_columns");
-        const TraceCheck r = check_trace(c, main_trace.ptr(), aux_trace.ptr(), n, challenges, weight_seed, capacity);
+        t.extend(c, n, challenges);
+        const TraceCheck r = check_trace(c, t.main_trace.ptr(), t.aux_trace.ptr(), n, challenges, weight_seed, capacity);
         *failing_rows = r.failing_rows;
         *n_failures = r.failures.size() / 2;
         if (!r.failures.empty()) std::memcpy(h_failures, r.failures.data(), r.failures.size() * sizeof(u64));
-        return TVM_OK;
-    } catch (const Error& e) {
-        if (error && error_capacity) std::snprintf(error, error_capacity, "%s", e.what());
-        return e.status ? e.status : TVM_ERR_INVALID_ARGUMENT;
-    } catch (const std::exception& e) {
-        if (error && error_capacity) std::snprintf(error, error_capacity, "%s", e.what());
-        return TVM_ERR_DEVICE;
-    }
+    });
 }
 
 // Stir::prove alone, for an explicitly given instance (the tests' small instances; Stark::stir derives them otherwise):
@@ -1205,7 +1216,7 @@ extern "C" int32_t tvmh_stir_prove(tvm_ctx* ctx, tvm_domain initial_domain, uint
                                    const uint64_t* d_codeword, uint64_t* h_first_round_indices, uint64_t* h_proof, uint64_t capacity,
                                    uint64_t* proof_words, char* error, uint64_t error_capacity) {
     using namespace triton_vm;
-    try {
+    return guarded(error, error_capacity, [&] {
         const Context c(ctx);
         Stir stir;
         stir.initial_domain = ArithmeticDomain{initial_domain.offset, initial_domain.generator, initial_domain.length};
@@ -1216,17 +1227,8 @@ extern "C" int32_t tvmh_stir_prove(tvm_ctx* ctx, tvm_domain initial_domain, uint
         ProofStream ps;
         const std::vector<u64> first = stir.prove(c, d_codeword, ps);
         if (h_first_round_indices) std::memcpy(h_first_round_indices, first.data(), first.size() * sizeof(u64));
-        const std::vector<u64> proof = ps.proof();
-        if (proof_words) *proof_words = proof.size();
-        if (h_proof && capacity >= proof.size()) std::memcpy(h_proof, proof.data(), proof.size() * sizeof(u64));
-        return TVM_OK;
-    } catch (const Error& e) {
-        if (error && error_capacity) std::snprintf(error, error_capacity, "%s", e.what());
-        return e.status ? e.status : TVM_ERR_INVALID_ARGUMENT;
-    } catch (const std::exception& e) {
-        if (error && error_capacity) std::snprintf(error, error_capacity, "%s", e.what());
-        return TVM_ERR_DEVICE;
-    }
+        copy_proof_out(ps.proof(), h_proof, capacity, proof_words);
+    });
 }
 
 // Stark::stir's instance for a padded height: out = [initial domain length, folding factor, final in-domain queries, final

@@ -193,14 +193,12 @@ public:
            const u64* d_aux_trace, const u64* d_aux_randomizers, const std::vector<Xfe>& quotient_randomizer,
            const Claim& claim = Claim());
     ProofStream prove();  // the hot path of Prover::prove, stark.rs:331-719
-    std::vector<Xfe> last_polynomial;
     // called with the 63 challenges before the auxiliary table is extended: MasterMainTable::extend for a prover that
     // starts from an execution trace (prove_execution); the auxiliary trace buffer is filled then
     std::function<void(const std::vector<Xfe>&)> extend;
     bool assume_valid_trace = false;  // TVM_OPTION_AIR_VALID_TRACE around the quotient evaluation
 
 private:
-    std::vector<u64> fri(const DeviceBuffer& combination, ProofStream& ps);  // Fri::prove, fri.rs:212-319
     const Context& c_;
     StarkParameters p_;
     Claim claim_;
@@ -223,7 +221,13 @@ void offset_rng_seed(const uint8_t seed[32], u64 offset, uint8_t out[32]);
 struct ExecutionTables {
     DeviceBuffer main_trace, main_rnd, aux_trace, aux_rnd;
     std::vector<Xfe> quotient_randomizer;
+    ExecutionTables() = default;
+    // the trace randomizers and the quotient randomizer, then fill_trace
     ExecutionTables(const Context& c, const StarkParameters& p, const tvm_aet& aet, const uint8_t seed[32],
+                    const std::function<void(const char*)>& lap);
+    // the trace part alone (tvmh_check_execution draws no randomizers): fill, length check, pad, derived main columns, the
+    // batch-randomizer column
+    void fill_trace(const Context& c, u64 n_rows, u64 padded_height, const tvm_aet& aet, const uint8_t seed[32],
                     const std::function<void(const char*)>& lap);
     void extend(const Context& c, u64 n_rows, const std::vector<Xfe>& challenges) const;
 };

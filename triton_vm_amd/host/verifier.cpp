@@ -551,18 +551,15 @@ extern "C" int32_t tvmh_verify(tvm_ctx* ctx, const uint64_t* h_proof, uint64_t p
                                char* error, uint64_t error_capacity) {
     using namespace triton_vm;
     if (error && error_capacity) error[0] = 0;
-    try {
+    return guarded(error, error_capacity, [&] {
         if (!ctx || !verdict || (!h_proof && proof_words) || (n_public_input && !h_public_input) || (n_public_output && !h_public_output))
             throw Error(TVM_ERR_INVALID_ARGUMENT, "tvmh_verify: null context, verdict, proof or claim");
         if (ldt_choice > 2) throw Error(TVM_ERR_INVALID_ARGUMENT, "tvmh_verify: the LDT choice is 0 (FRI), 1 (STIR) or 2 (Stark::ldt's rule)");
         if (!security_level || security_level > 512 || !log2_expansion || log2_expansion > 8)
             throw Error(TVM_ERR_INVALID_ARGUMENT, "tvmh_verify: security level 1..512, log2 expansion 1..8");
         const Context c(ctx);
-        Claim claim;
+        Claim claim = make_claim(h_program_digest, h_public_input, n_public_input, h_public_output, n_public_output);
         claim.version = version;
-        if (h_program_digest) std::memcpy(claim.program_digest, h_program_digest, sizeof(claim.program_digest));
-        if (n_public_input) claim.input.assign(h_public_input, h_public_input + n_public_input);
-        if (n_public_output) claim.output.assign(h_public_output, h_public_output + n_public_output);
         Verifier verifier(c, security_level, log2_expansion, ldt_choice);
         auto stages = [&]() {
             if (stage_ms) std::memcpy(stage_ms, verifier.stage_ms, sizeof(verifier.stage_ms));
@@ -579,12 +576,5 @@ extern "C" int32_t tvmh_verify(tvm_ctx* ctx, const uint64_t* h_proof, uint64_t p
             *verdict = f.verdict;
             if (error && error_capacity) std::snprintf(error, error_capacity, "%s", verdict_name(f.verdict));
         }
-        return TVM_OK;
-    } catch (const Error& e) {
-        if (error && error_capacity) std::snprintf(error, error_capacity, "%s", e.what());
-        return e.status ? e.status : TVM_ERR_INVALID_ARGUMENT;
-    } catch (const std::exception& e) {
-        if (error && error_capacity) std::snprintf(error, error_capacity, "%s", e.what());
-        return TVM_ERR_DEVICE;
-    }
+    });
 }
