@@ -407,6 +407,56 @@ int32_t tvm_deep_codeword(tvm_ctx* ctx, uint32_t n_components, const uint64_t* c
                           const uint64_t* h_points, const uint64_t* h_values, const uint64_t* h_weights,
                           uint64_t* d_out);
 
+/* ---- the PROOF TAIL: what follows the commit phase of Fri::prove (fri.rs:265-319) and the trace openings of Prover::prove
+ * (stark.rs:665-716) with the transcript on the device (csrc/proof_tail.hip) ------------------------------------
+ * Tip5::sample_indices [twenty-first] (proof_stream.rs:86-104) on the device, squeezing straight from the given sponge state (no
+ * item is absorbed): the rate is read, an element whose canonical value is p - 1 is skipped, the others give value % upper_bound,
+ * and the state is permuted whenever its ten rate words are used up.  upper_bound: a power of two, at most 2^32; n <= 2^16.
+ * h_indices_out: n words; h_state_out: the 16 words of the sponge afterwards.  One launch, one synchronisation. */
+int32_t tvm_sponge_sample_indices(tvm_ctx* ctx, const uint64_t* h_state, uint64_t upper_bound, uint64_t n,
+                                  uint64_t* h_indices_out, uint64_t* h_state_out);
+/* MerkleTree::authentication_structure [twenty-first] for n_trees trees at once, ONE launch (a workgroup per tree) and ONE
+ * synchronisation.  Tree j has n_leaves[j] leaves (a power of two, 1 .. TVM_VERIFIER_MAX_LEAVES) and is opened at the n_indices[j]
+ * leaf indices h_indices[j] (any order, duplicates allowed, at most TVM_TAIL_MAX_INDICES).  h_node_indices_out[j]: the heap indices
+ * of the nodes a verifier cannot compute from the opened leaves, in descending heap order -- room for
+ * min(n_indices[j], n_leaves[j]) * log2(n_leaves[j]) words; n_out[j]: their number.  d_nodes[j] (the array may be null, and so
+ * may any entry): the tree's nodes [2 n_leaves][5] on the device, as tvm_merkle_tree writes them -- h_nodes_out[j] then receives
+ * the n_out[j] digests at those heap indices; a null entry plans the index list alone, for a tree that is not in memory.
+ * TVM_NOT_APPLICABLE and nothing written when a tree has more than TVM_TAIL_MAX_INDICES indices. */
+#define TVM_TAIL_MAX_INDICES 1024u
+int32_t tvm_authentication_structures(tvm_ctx* ctx, uint32_t n_trees, const uint64_t* n_leaves, const uint64_t* const* h_indices,
+                                      const uint64_t* n_indices, const uint64_t* const* d_nodes, uint64_t* const* h_node_indices_out,
+                                      uint64_t* const* h_nodes_out, uint64_t* n_out);
+/* Everything of a FRI proof after the commit phase, and the trace openings, without the host in between.  d_codeword, domain,
+ * n_rounds, d_codewords and d_nodes are the arguments of tvm_fri_commit_phase after it has returned; h_sponge_state is the sponge
+ * after the commit phase's enqueues and samplings.  On the stream: the last codeword is interpolated (over the domain of its
+ * length with offset 1); ProofItem::Polynomial(last polynomial, trailing zeros dropped) is absorbed (proof_stream.rs:54-59; the
+ * last codeword is a proof item outside the Fiat-Shamir heuristic, proof_item.rs:96-150, and is only handed back);
+ * n_checks indices are sampled below domain.length (the `a` indices);
+ * the authentication structures of every answered round are computed; and the payloads of the items that follow are written in
+ * proof-item order:
+ *     round 0 at the a indices: leaves, authentication structure
+ *     rounds 0 .. n_rounds - 1 at the b indices (a mod n + n/2) mod n, n the round's length: leaves, authentication structure
+ *     main rows, main authentication structure, aux rows, aux ..., quotient-segment rows, quotient ...: the rows of tables[0..2] on
+ *     the view of ldt_length rows (as tvm_table_reveal_rows) at the a indices; the three trees d_table_nodes[0..2] share the
+ *     structure of round 0 at the a indices.  ldt_length must be domain.length.
+ * That is TVM_TAIL_ITEMS(n_rounds) payloads.  h_directory [items][2]: (offset, words) of each payload in h_payload;
+ * *payload_words: their sum -- they are copied when payload_capacity suffices, TVM_ERR_INVALID_ARGUMENT otherwise
+ * (tvm_fri_query_and_open_payload_bound words always suffice). h_state_out: the sponge after the sampling (16 words); h_indices_out: n_checks
+ * words; h_last_codeword, h_last_polynomial: 3 * (domain.length >> n_rounds) words each (the polynomial with its trailing zeros).
+ * The caller replays the two enqueues and the sampling on its own sponge, which must arrive at h_state_out and h_indices_out.
+ * Two stream synchronisations: the fixed-size part, then the payload.  TVM_NOT_APPLICABLE and nothing written when
+ * n_checks > TVM_TAIL_MAX_INDICES. */
+#define TVM_TAIL_ITEMS(n_rounds) (2u * ((n_rounds) ? (n_rounds) + 1u : 1u) + 6u)
+int32_t tvm_fri_query_and_open(tvm_ctx* ctx, const uint64_t* h_sponge_state, const uint64_t* d_codeword, tvm_domain domain,
+                               uint32_t n_rounds, const uint64_t* const* d_codewords, const uint64_t* const* d_nodes,
+                               uint64_t n_checks, const tvm_table* const* tables, const uint64_t* const* d_table_nodes,
+                               uint64_t ldt_length, uint64_t* h_state_out, uint64_t* h_indices_out, uint64_t* h_last_codeword,
+                               uint64_t* h_last_polynomial, uint64_t* h_directory, uint64_t* h_payload, uint64_t payload_capacity,
+                               uint64_t* payload_words);
+/* an upper bound of *payload_words: every response and opening with an authentication structure of n_checks full paths */
+uint64_t tvm_fri_query_and_open_payload_bound(tvm_domain domain, uint32_t n_rounds, uint64_t n_checks, const tvm_table* const* tables);
+
 /* ---- F1: ProverRound::split_and_fold (fri.rs:349-366): domain.length XFE -> domain.length/2 XFE */
 int32_t tvm_fri_split_and_fold(tvm_ctx* ctx, const uint64_t* d_codeword, tvm_domain domain,
                                const uint64_t* h_challenge, uint64_t* d_out);

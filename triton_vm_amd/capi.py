@@ -136,6 +136,13 @@ _SIGNATURES = {
     "tvm_fri_commit_phase": (C.c_int32, [C.c_void_p, C.c_void_p, Domain, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                          C.c_void_p]),
     "tvm_gather_elements_batch": (C.c_int32, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "tvm_sponge_sample_indices": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p]),
+    "tvm_authentication_structures": (C.c_int32, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                  C.c_void_p, C.c_void_p]),
+    "tvm_fri_query_and_open": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, Domain, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64,
+                                           C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                           C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "tvm_fri_query_and_open_payload_bound": (C.c_uint64, [Domain, C.c_uint32, C.c_uint64, C.c_void_p]),
     "tvm_verifier_row_digests": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p]),
     "tvm_verifier_deep_values": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, Domain,
                                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -127,9 +127,15 @@ protected:
     virtual std::vector<FriAnswer> answer_distributed(const std::vector<FriQuery>& /*queries*/) { return {}; }
     // 19: the rows of the three tables at `indices` and the authentication structures of the three trees
     virtual Openings open(const tvm_table* segments, const std::vector<u64>& indices) = 0;
+    // TVMH_OPTION_DEVICE_TAIL: the three tables (main, aux, quotient segments) extended over the whole LDT domain and their whole
+    // trees, where this prover has them (the single-GPU one); false: the proof's tail keeps the host's path
+    virtual bool whole_tables_and_trees(const tvm_table* /*tables*/[3], const u64* /*trees*/[3]) { return false; }
 
 private:
     std::vector<u64> fri(DeviceBuffer&& combination);   // -> the first-round indices
+    bool fri_device_tail(const std::vector<FriRound>& rounds, std::vector<u64>& a_indices);
+    Openings tail_openings;   // the openings of step 19 when fri_device_tail has fetched them
+    bool have_tail_openings = false;
 };
 
 // ---- what every extern "C" entry point does around its body ------------------------------------------------------------

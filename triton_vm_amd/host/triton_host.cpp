@@ -11,6 +11,7 @@
 #include <cstring>
 #include <exception>
 #include <iterator>
+#include <memory>
 #include <thread>
 
 namespace triton_vm {
@@ -498,6 +499,8 @@ std::vector<u64> ProofSteps::fri(DeviceBuffer&& combination) {
     ArithmeticDomain dom = p.ldt;
     owned.push_back(fri_distributed_rounds(std::move(combination), rounds, dom));
     const u64* cw = owned.back().ptr();
+    const size_t first_whole_round = rounds.size();
+    std::vector<u64> a_indices_tail;
     if (rounds.size() <= p.fri_rounds) {
         // The commit phase in one call, the sponge on the device (tvm_fri_commit_phase): trees, roots into the transcript,
         // folding challenges, folds -- then the same enqueues and samplings are replayed on this host's sponge, which must
@@ -526,6 +529,10 @@ std::vector<u64> ProofSteps::fri(DeviceBuffer&& combination) {
         }
         cw = rounds.back().cw;
         dom = rounds.back().dom;
+    }
+    if (first_whole_round == 0 && tvmh_get_option(TVMH_OPTION_DEVICE_TAIL) && fri_device_tail(rounds, a_indices_tail)) {
+        (void)ps.sample_scalars(1);
+        return a_indices_tail;
     }
     std::vector<u64> last(dom.length * 3);
     c.check(tvm_memcpy_d2h(c.raw(), last.data(), cw, last.size() * sizeof(u64)), "last codeword");
@@ -571,6 +578,53 @@ std::vector<u64> ProofSteps::fri(DeviceBuffer&& combination) {
     }
     (void)ps.sample_scalars(1);
     return a_indices;
+}
+
+static std::atomic<uint64_t> g_device_tail_proofs{0};   // tvmh_device_tail_proofs
+// TVMH_OPTION_DEVICE_TAIL: everything of Fri::prove behind the commit phase (fri.rs:265-319) and the trace openings of step 19 in one
+// call, the sponge on the device (tvm_fri_query_and_open) -- then the two enqueues and the sampling are replayed on this host's sponge,
+// which must arrive at the same indices and the same state.  false: the call does not apply (no whole tables and trees here, more
+// checks than TVM_TAIL_MAX_INDICES) and nothing was enqueued.
+bool ProofSteps::fri_device_tail(const std::vector<FriRound>& rounds, std::vector<u64>& a_indices) {
+    const tvm_table* tables[3];
+    const u64* table_nodes[3];
+    if (!whole_tables_and_trees(tables, table_nodes)) return false;
+    const uint32_t n_rounds = (uint32_t)rounds.size() - 1, n_items = TVM_TAIL_ITEMS(n_rounds);
+    const u64 n_last = rounds.back().dom.length, q = p.num_collinearity_checks;
+    std::vector<const u64*> d_cw, d_nodes;
+    for (size_t r = 0; r < rounds.size(); r++) {
+        if (r) d_cw.push_back(rounds[r].cw);
+        d_nodes.push_back(rounds[r].nodes.ptr());
+    }
+    u64 state[16], n_payload = 0;
+    std::vector<u64> indices(q), last(3 * n_last), last_poly(3 * n_last), directory(2 * (size_t)n_items);
+    // (room for the bound -- every list n_checks full paths, some MB at 2^20 rows -- but not filled: only the pages the proof's words reach are touched)
+    const u64 capacity = tvm_fri_query_and_open_payload_bound(rounds[0].dom.c(), n_rounds, q, tables);
+    const std::unique_ptr<u64[]> payload(new u64[capacity ? capacity : 1]);
+    const int32_t status = tvm_fri_query_and_open(c.raw(), ps.sponge_state(), rounds[0].cw, rounds[0].dom.c(), n_rounds, d_cw.data(), d_nodes.data(), q,
+                                                  tables, table_nodes, p.ldt.length, state, indices.data(), last.data(), last_poly.data(),
+                                                  directory.data(), payload.get(), capacity, &n_payload);
+    if (status == TVM_NOT_APPLICABLE) return false;
+    c.check(status, "tvm_fri_query_and_open");
+    ps.enqueue("fri last codeword", last.data(), last.size());
+    ps.enqueue("fri last polynomial", last_poly.data(), last_poly.size());
+    a_indices = ps.sample_indices(p.ldt.length, q);
+    if (a_indices != indices || std::memcmp(state, ps.sponge_state(), sizeof(state)) != 0)
+        throw Error(TVM_ERR_DEVICE, "the device's Fiat-Shamir sponge and the host's disagree on the FRI query indices");
+    auto item = [&](size_t k) { return std::make_pair(payload.get() + directory[2 * k], directory[2 * k + 1]); };
+    for (size_t k = 0; 2 * k + 6 < n_items; k++) {   // round 0 at the a indices, then rounds 0 .. n_rounds - 1 at the b indices
+        const std::string round = std::to_string(k ? k - 1 : 0);
+        ps.enqueue("fri response " + round, item(2 * k).first, item(2 * k).second);
+        ps.enqueue("fri auth " + round, item(2 * k + 1).first, item(2 * k + 1).second);
+    }
+    for (int w = 0; w < 3; w++) {   // kept for step 19
+        const size_t k = n_items - 6 + 2 * (size_t)w;
+        tail_openings.rows[w].assign(item(k).first, item(k).first + item(k).second);
+        tail_openings.auth[w].assign(item(k + 1).first, item(k + 1).first + item(k + 1).second);
+    }
+    have_tail_openings = true;
+    g_device_tail_proofs++;
+    return true;
 }
 
 void ProofSteps::segment_combinations(const tvm_table* segments, const DeviceBuffer&, u64, const ArithmeticDomain& short_rank, const Xfe* wp,
@@ -707,7 +761,7 @@ ProofStream ProofSteps::prove() {
     // 19: open the trace leafs  (stark.rs:665-716)
     mark("open trace leafs");
     {
-        const Openings o = open(seg.t, a_indices);
+        const Openings o = have_tail_openings ? std::move(tail_openings) : open(seg.t, a_indices);
         ps.enqueue("main rows", o.rows[MAIN].data(), o.rows[MAIN].size());
         ps.enqueue("main auth", o.auth[MAIN].data(), o.auth[MAIN].size());
         ps.enqueue("aux rows", o.rows[AUX].data(), o.rows[AUX].size());
@@ -726,9 +780,29 @@ namespace {
 struct WholeSteps : ProofSteps {
     using ProofSteps::ProofSteps;
     DeviceBuffer nodes[3];   // the three Merkle trees, by Which
+    // TVMH_OPTION_TRACE: the stages of the hot path on stderr beside Stopwatch's laps (1: the stream drained at every boundary)
+    const uint64_t trace = tvmh_get_option(TVMH_OPTION_TRACE);
+    std::chrono::steady_clock::time_point stage_start;
+    std::string stage;
+    void mark(const char* next) override {
+        if (!trace) return;
+        if (trace == 1) (void)tvm_sync(c.raw());
+        const auto now = std::chrono::steady_clock::now();
+        if (!stage.empty()) std::fprintf(stderr, "[tvmh]   %-26s %8.3f ms\n", stage.c_str(), std::chrono::duration<double, std::milli>(now - stage_start).count());
+        stage = next, stage_start = now;
+    }
+    ~WholeSteps() { mark(""); }   // (the last stage ends with the proof)
 
     void extend_master_table(Which w) override { master(w).maybe_low_degree_extend_all_columns(); }
+    const tvm_table* segment_table = nullptr;   // as commit(QUOT, ..) saw it
+    bool whole_tables_and_trees(const tvm_table* tables[3], const u64* trees[3]) override {
+        if (!segment_table || !nodes[MAIN].ptr() || !nodes[AUX].ptr() || !nodes[QUOT].ptr()) return false;
+        tables[MAIN] = main.table(), tables[AUX] = aux.table(), tables[QUOT] = segment_table;
+        for (int w = 0; w < 3; w++) trees[w] = nodes[w].ptr();
+        return true;
+    }
     Words commit(Which w, const tvm_table* segments) override {
+        if (w == QUOT) segment_table = segments;
         nodes[w] = DeviceBuffer(c, 10 * p.ldt.length);
         c.check(tvm_table_merkle_tree(c.raw(), w == QUOT ? segments : master(w).table(), p.ldt.length, nodes[w].ptr()), "tvm_table_merkle_tree");
         return merkle_root(c, nodes[w]);
@@ -1123,11 +1197,13 @@ std::vector<u64> prove_execution(const Context& c, const StarkParameters& p, con
 
 }  // namespace triton_vm
 
-static std::atomic<uint64_t> g_options[6] = {{0}, {0}, {0}, {0}, {0}, {0}};   // indexed by TVMH_OPTION_*
+static std::atomic<uint64_t> g_options[7] = {{0}, {0}, {0}, {0}, {0}, {0}, {0}};   // indexed by TVMH_OPTION_*
 extern "C" void tvmh_set_option(uint32_t option, uint64_t value) {
-    if (option >= 1 && option <= 5) g_options[option].store(value);
+    if (option >= 1 && option <= 6) g_options[option].store(value);
 }
-extern "C" uint64_t tvmh_get_option(uint32_t option) { return option >= 1 && option <= 5 ? g_options[option].load() : 0; }
+extern "C" uint64_t tvmh_get_option(uint32_t option) { return option >= 1 && option <= 6 ? g_options[option].load() : 0; }
+
+extern "C" uint64_t tvmh_device_tail_proofs(void) { return triton_vm::g_device_tail_proofs.load(); }
 
 extern "C" int32_t tvmh_prove(tvm_ctx* ctx, uint32_t log2_padded_height, uint64_t num_trace_randomizers,
                               uint64_t num_collinearity_checks, uint32_t log2_expansion, const uint64_t* d_main_trace,

@@ -497,7 +497,9 @@ extern "C" int32_t tvmh_check_execution(tvm_ctx* ctx, const tvm_aet* aet, uint32
 // at 2^22 rows); the stage times of ranks 1..N-1 then lack the replicated stages, rank 0's has them.  Default 0.
 #define TVMH_OPTION_SHARE_REPLICATED_TABLES 2
 // TVMH_OPTION_TRACE != 0: host wall time of the steps of prove_execution (plain and sharded) on stderr.  Diagnostics only; the host
-// library, like the backend, reads no environment variable.
+// library, like the backend, reads no environment variable.  The single-GPU prover (tvmh_prove, tvmh_prove_execution) also prints one
+// indented line per stage of the hot path ("FRI", "open trace leafs", ...); with the value 1 it drains the stream at each of those stage
+// boundaries as well, so the "prove" lap of value 1 is the sum of drained stages, not a proof's latency -- value 2 drains nothing.
 #define TVMH_OPTION_TRACE 3
 // TVMH_OPTION_COLUMN_SPLIT = k > 0: the sharded prover splits the INVERSE transforms of the table extensions by columns over the
 // ranks and exchanges the coefficients in k chunks per table (MasterTable::low_degree_extend_over) instead of replicating them --
@@ -510,6 +512,16 @@ extern "C" int32_t tvmh_check_execution(tvm_ctx* ctx, const tvm_aet* aet, uint32
 // fails in exact mode -- the reference's proof, word for word -- reporting the fallback under TVMH_OPTION_TRACE.  Default 0.  The
 // sharded / coset-wise entry points (and prove_execution's fallback to them on out-of-memory) refuse it: TVM_ERR_UNSUPPORTED.
 #define TVMH_OPTION_CHECK_TRACE 5
+// TVMH_OPTION_DEVICE_TAIL != 0: a single-GPU FRI proof runs everything behind FRI's commit phase -- the last polynomial into the sponge
+// (the last codeword is a proof item outside the Fiat-Shamir heuristic: it is only fetched), the query indices, every round's leaves
+// and authentication structure -- and the trace openings of step 19 in one
+// call with the sponge on the device (tvm_fri_query_and_open: two stream synchronisations instead of seven, no host work in between);
+// the host replays the two enqueues and the sampling on its own sponge and throws TVM_ERR_DEVICE when indices or state differ.  The
+// same proof, word for word.  Default 0.  STIR proofs, the sharded and coset-wise provers, and a proof with more than
+// TVM_TAIL_MAX_INDICES collinearity checks (TVM_NOT_APPLICABLE) keep the host's path whatever the value.
+#define TVMH_OPTION_DEVICE_TAIL 6
+// how many proofs of this process took that path so far (a proof it does not apply to is not counted: tests and the timing tool ask)
+extern "C" uint64_t tvmh_device_tail_proofs(void);
 extern "C" void tvmh_set_option(uint32_t option, uint64_t value);
 extern "C" uint64_t tvmh_get_option(uint32_t option);
 

@@ -49,6 +49,8 @@ def load_host_library(backend_path=None, out=None):
     lib.tvmh_set_option.argtypes = [C.c_uint32, C.c_uint64]
     lib.tvmh_get_option.restype = C.c_uint64
     lib.tvmh_get_option.argtypes = [C.c_uint32]
+    lib.tvmh_device_tail_proofs.restype = C.c_uint64
+    lib.tvmh_device_tail_proofs.argtypes = []
     lib.tvmh_local_comms_create.restype = C.c_int32
     lib.tvmh_local_comms_create.argtypes = [C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)]
     lib.tvmh_local_comms_destroy.restype = None
@@ -65,6 +67,7 @@ OPTION_SHARE_REPLICATED_TABLES = 2   # in-process ranks use ONE copy of the repl
 OPTION_TRACE = 3   # host wall time of the steps of prove_execution on stderr
 OPTION_COLUMN_SPLIT = 4   # k > 0: the sharded prover splits the inverse transforms by columns, coefficients exchanged in k chunks
 OPTION_CHECK_TRACE = 5   # prove_execution checks the AIR on the trace first and proves a trace that fails in exact mode
+OPTION_DEVICE_TAIL = 6   # single-GPU FRI proofs: the query phase and the trace openings in one device round trip (proof_tail.py)
 
 
 class host_option:
