@@ -457,6 +457,47 @@ int32_t tvm_fri_query_and_open(tvm_ctx* ctx, const uint64_t* h_sponge_state, con
 /* an upper bound of *payload_words: every response and opening with an authentication structure of n_checks full paths */
 uint64_t tvm_fri_query_and_open_payload_bound(tvm_domain domain, uint32_t n_rounds, uint64_t n_checks, const tvm_table* const* tables);
 
+/* ---- the ROUNDS OF STIR: the whole of Stir::prove (stir.rs:885-993) with the transcript on the device, without the host in between
+ * (csrc/stir_rounds.hip).  d_codeword: domain.length XFE, the codeword to be proven close to low degree;
+ * round_queries [n_rounds][2] = (in-domain queries, out-of-domain queries) of the full rounds, final_queries those of the final
+ * round, final_degree the instance's bound on the final polynomial (below domain.length / folding_factor^(n_rounds + 1), the
+ * number of coefficients handed back); folding_factor: a power of two, 2 .. 16.  h_sponge_state: the sponge before Stir::prove.
+ * On the stream, per full round r: sample_scalars(1) (the folding randomness); the folded polynomial, its codeword on the next
+ * round's domain, the stacked Merkle tree of that (tree r + 1; tree 0 is over d_codeword), ProofItem::MerkleRoot absorbed;
+ * sample_scalars(n_ood) (the out-of-domain points); the folded polynomial there, ProofItem::StirOutOfDomainValues absorbed (also
+ * when it is empty); sample_indices(the round's domain length, n_in_domain); sample_scalars(1) (the degree-correction randomness);
+ * the indices mod the folded domain's length without repeats, in order of first occurrence; the quotient set, the answer
+ * polynomial and the next round's witness polynomial (as tvm_xfe_interpolate and tvm_stir_next_polynomial).  The final round:
+ * sample_scalars(1), the fold, ProofItem::Polynomial absorbed, sample_indices(its domain's length, final_queries).  Then the
+ * StirResponse payloads of trees 0 .. n_rounds in proof-item order -- per tree: the stacked leaves (folding_factor XFE per index, at
+ * the indices without repeats), the authentication structure -- packed into h_payload.
+ *   h_state_out         16 words: the sponge at the end
+ *   h_roots             [n_rounds + 1][5]
+ *   h_scalars           every sampled scalar in transcript order: per full round the folding randomness, the n_ood out-of-domain
+ *                       points, the degree-correction randomness; then the final folding randomness: 3 (2 n_rounds + 1 + sum n_ood) words
+ *   h_ood_values        [sum n_ood][3], round by round (may be null when there are none)
+ *   h_indices           the sampled indices of rounds 0 .. n_rounds, one list behind the other (sum of the in-domain query counts words)
+ *   h_unique            the same shape: each round's indices without repeats at the place of its sampled ones, h_unique_counts
+ *                       [n_rounds + 1] of them valid
+ *   h_final_polynomial  domain.length / folding_factor^(n_rounds + 1) XFE, with its trailing zeros
+ *   h_directory         [2 (n_rounds + 1)][2]: (offset, words) of each payload in h_payload; *payload_words: their sum -- they are
+ *                       copied when payload_capacity suffices, TVM_ERR_INVALID_ARGUMENT otherwise
+ *                       (tvm_stir_prove_rounds_payload_bound words always suffice)
+ * The caller replays every enqueue and every sampling on its own sponge, which must arrive at the same scalars, indices and state.
+ * Two stream synchronisations: the fixed-size part, then the payload.  TVM_NOT_APPLICABLE, nothing written and nothing queued when a
+ * round (the final one included) has more than TVM_TAIL_MAX_INDICES in-domain queries, or a full round more than 256 queries in all
+ * (the limit of the one-workgroup interpolation; the final round has no quotient set).  TVM_ERR_INVALID_ARGUMENT afterwards if two points of a quotient set coincide. */
+int32_t tvm_stir_prove_rounds(tvm_ctx* ctx, const uint64_t* h_sponge_state, const uint64_t* d_codeword, tvm_domain domain,
+                              uint32_t folding_factor, uint32_t n_rounds, const uint64_t* round_queries, uint64_t final_queries,
+                              uint64_t final_degree, uint64_t* h_state_out, uint64_t* h_roots, uint64_t* h_scalars,
+                              uint64_t* h_ood_values, uint64_t* h_indices, uint64_t* h_unique, uint64_t* h_unique_counts,
+                              uint64_t* h_final_polynomial, uint64_t* h_directory, uint64_t* h_payload, uint64_t payload_capacity,
+                              uint64_t* payload_words);
+/* an upper bound of *payload_words: every response with all its indices distinct and full authentication paths; 0 where
+ * tvm_stir_prove_rounds does not apply */
+uint64_t tvm_stir_prove_rounds_payload_bound(tvm_domain domain, uint32_t folding_factor, uint32_t n_rounds, const uint64_t* round_queries,
+                                             uint64_t final_queries);
+
 /* ---- F1: ProverRound::split_and_fold (fri.rs:349-366): domain.length XFE -> domain.length/2 XFE */
 int32_t tvm_fri_split_and_fold(tvm_ctx* ctx, const uint64_t* d_codeword, tvm_domain domain,
                                const uint64_t* h_challenge, uint64_t* d_out);

@@ -143,6 +143,10 @@ _SIGNATURES = {
                                            C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                            C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
     "tvm_fri_query_and_open_payload_bound": (C.c_uint64, [Domain, C.c_uint32, C.c_uint64, C.c_void_p]),
+    "tvm_stir_prove_rounds": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, Domain, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint64, C.c_uint64,
+                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                          C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "tvm_stir_prove_rounds_payload_bound": (C.c_uint64, [Domain, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint64]),
     "tvm_verifier_row_digests": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p]),
     "tvm_verifier_deep_values": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, Domain,
                                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -43,6 +43,8 @@ int xfe_interpolate(tvm_ctx* c, const u64* d_points, const u64* d_values, int k,
 int stir_fold_polynomial(tvm_ctx* c, const u64* poly, u64 n, int ff, const u64* h_r, u64* out);
 int stir_quotient(tvm_ctx* c, u64* vals, u64 n, u64 offset, u64 gen, const u64* d_points, const u64* d_answer,
                   const u64* d_answer_values, u32 k, u32 kb, const u64* h_r);
+// (stir_kernels.h: the work-items of the three kernels above, shared with stir_rounds.hip, whose launches take these small arguments
+// from device memory; tail_kernels.h: the launches of proof_tail.hip that stir_rounds.hip shares)
 // fill.hip
 int fill_degree_lowering(tvm_ctx* c, int table, u64* d_main, u64* d_aux, const u64* d_challenges, u64 n);
 // bezout.hip

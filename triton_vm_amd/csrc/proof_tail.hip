@@ -16,6 +16,7 @@
 
 #include "context.h"
 #include "kernels.h"
+#include "tail_kernels.h"
 #include "tip5.h"
 
 namespace tvm {
@@ -42,42 +43,8 @@ __global__ void __launch_bounds__(64) k_sponge_tail(SpongeTailArgs g) {
     tip5_stage_lut(lut, threadIdx.x, blockDim.x);
     const int lane = (int)threadIdx.x, pos = lane & 15;
     u64 x = g.state[pos];
-    if (g.polynomial) {
-        const u64* w = g.polynomial;
-        u32 n = 0;   // Polynomial drops its trailing zero coefficients: one past the highest non-zero one, over the wavefront
-        for (u32 e = (u32)lane; e < g.n_coefficients; e += 64)
-            if (w[3 * (u64)e] | w[3 * (u64)e + 1] | w[3 * (u64)e + 2]) n = e + 1;
-        for (int m = 32; m; m >>= 1) {
-            const u32 other = (u32)__shfl_xor((u64)n, m, 64);
-            n = other > n ? other : n;
-        }
-        const u64 n_prefix = 4, total = n_prefix + 3 * (u64)n;
-        // (the prefix words by selection, not from an indexed array: no scratch)
-        const u64 p0 = bfe_from_u64(g.discriminant), p1 = bfe_from_u64(total - 2), p2 = bfe_from_u64(total - 3), p3 = bfe_from_u64(n);
-        for (u64 b = 0; b * TIP5_RATE <= total; b++) {   // total / 10 + 1 blocks: the last one holds the padding
-            if (pos < TIP5_RATE) {
-                const u64 wi = b * TIP5_RATE + (u64)pos;
-                if (wi < n_prefix) x = wi == 0 ? p0 : wi == 1 ? p1 : wi == 2 ? p2 : p3;
-                else if (wi < total) x = w[wi - n_prefix];
-                else x = wi == total ? TVM_ONE : 0;
-            }
-            x = tip5_permute_lanes(x, pos, lane, lut);
-        }
-    }
-    // Tip5::sample_indices: squeeze, skip p - 1, reduce; the squeezed elements left over when n is reached are dropped
-    u32 count = 0;
-    while (count < g.n_indices) {
-        if (lane < TIP5_RATE) rate[lane] = x;
-        __syncthreads();
-        for (int k = 0; k < TIP5_RATE && count < g.n_indices; k++) {
-            const u64 v = bfe_mul(rate[k], 1);   // the canonical value of a Montgomery word
-            if (v == TVM_P - 1) continue;
-            if (lane == 0) g.indices[count] = v & g.mask;
-            count++;
-        }
-        __syncthreads();   // (the rate words are read before the next squeeze overwrites them)
-        x = tip5_permute_lanes(x, pos, lane, lut);
-    }
+    if (g.polynomial) x = sponge_absorb_polynomial_lanes(x, pos, lane, lut, g.discriminant, g.polynomial, g.n_coefficients);
+    x = sponge_sample_indices_lanes(x, pos, lane, lut, rate, g.n_indices, g.mask, g.indices);
     if (lane < 16) g.state[pos] = x;
 }
 
@@ -88,39 +55,13 @@ __global__ void __launch_bounds__(64) k_sponge_tail(SpongeTailArgs g) {
 // levels below; the parents without repeats) come from ONE workgroup prefix sum over two packed 16-bit counters; no atomics.
 // Deeper levels have the larger heap indices, so this order is the descending heap order of MerkleTree::authentication_structure
 // (auth_node_indices, triton_host.cpp).
-struct AuthJob {
-    const u64* idx;     // [n_idx] on the device
-    u64 n_leaves, add;  // leaf i of the job = (idx[i] + add) & (n_leaves - 1): the a indices of a round, or its b indices (add = n/2)
-    u64* out_idx;       // heap indices out
-    const u64* nodes;   // null, or the tree [2 n_leaves][5]: out_nodes receives the digests at out_idx
-    u64* out_nodes;
-    u64 n_idx;
-};
-// inclusive prefix sum of v over the workgroup and the sum over all of it; the caller puts a barrier before the next call
-TVM_D u32 as_block_scan(u32 v, u32* wave_sums, u32& total) {
-    const int lane = (int)(threadIdx.x & 63);
-    const u32 wave = threadIdx.x >> 6, n_waves = blockDim.x >> 6;
-    for (int d = 1; d < 64; d <<= 1) {
-        const u32 below = (u32)__shfl((u64)v, lane - d, 64);
-        if (lane >= d) v += below;
-    }
-    if (lane == 63) wave_sums[wave] = v;
-    __syncthreads();
-    u32 before = 0;
-    total = 0;
-    for (u32 w = 0; w < n_waves; w++) {
-        const u32 s = wave_sums[w];
-        total += s;
-        if (w < wave) before += s;
-    }
-    return v + before;
-}
 __global__ void __launch_bounds__(TVM_TAIL_MAX_INDICES) k_authentication_structures(const AuthJob* __restrict__ jobs, u64* __restrict__ counts) {
     __shared__ u64 key[TVM_TAIL_MAX_INDICES];
     __shared__ u32 wave_sums[TVM_TAIL_MAX_INDICES / 64];
     const AuthJob job = jobs[blockIdx.x];
     const u32 tid = threadIdx.x, nt = blockDim.x;   // nt: a power of two, at least n_idx
-    key[tid] = tid < job.n_idx ? ((job.idx[tid] + job.add) & (job.n_leaves - 1)) + job.n_leaves : ~0ull;
+    const u64 n_idx = job.n_idx_device ? *job.n_idx_device : job.n_idx;
+    key[tid] = tid < n_idx ? ((job.idx[tid] + job.add) & (job.n_leaves - 1)) + job.n_leaves : ~0ull;
     __syncthreads();
     for (u32 size = 2; size <= nt; size <<= 1)   // bitonic sort, ascending; the padding sorts to the end
         for (u32 j = size >> 1; j; j >>= 1) {
@@ -134,7 +75,7 @@ __global__ void __launch_bounds__(TVM_TAIL_MAX_INDICES) k_authentication_structu
     u32 total, m;
     {   // without repeats
         const u64 x = key[tid];
-        const bool first = tid < job.n_idx && (tid == 0 || key[tid - 1] != x);
+        const bool first = tid < n_idx && (tid == 0 || key[tid - 1] != x);
         const u32 at = as_block_scan(first ? 1u : 0u, wave_sums, total);
         if (first) key[at - 1] = x;
         m = total;
@@ -166,23 +107,8 @@ __global__ void __launch_bounds__(TVM_TAIL_MAX_INDICES) k_authentication_structu
 // The payloads of the proof items behind the sampling, packed in proof-item order.  gridDim.y = the number of payloads ("segments"),
 // gridDim.x workgroups share a segment's words.  A segment's offset is the sum of the lengths before it, and those of the
 // authentication structures are only known on the device (counts of k_authentication_structures).
-struct TailSegment {
-    const u64* src;   // leaves: the round's codeword [n][3]; nodes: the tree [2 n][5]; rows: the table's storage
-    u64 mask, add;    // leaves: element (a[i] + add) & mask
-    u32 kind;         // 0: leaves at the a / b indices, 1: authentication nodes of list `which`, 2: rows of table `which` at the a indices
-    u32 which;
-};
-struct TailGatherArgs {
-    const TailSegment* segments;
-    const u64 *a, *auth_idx, *auth_counts;   // [n_checks]; [n_lists][auth_stride]; [n_lists]
-    u64 n_checks, auth_stride;
-    TabLayout layout[3];                     // the three tables
-    u64 row_stride[3];                       // rows of a table per row of its LDT-domain view
-    u32 W[3];
-    u64 *out, *directory;                    // packed payloads; [segments][2] = (offset, words)
-};
 TVM_D u64 tg_words(const TailGatherArgs& g, const TailSegment& s) {
-    return s.kind == 0 ? 3 * g.n_checks : s.kind == 1 ? 5 * g.auth_counts[s.which] : (u64)g.W[s.which] * g.n_checks;
+    return s.kind == 0 ? 3 * (u64)(s.stack ? s.stack : 1) * (s.count ? *s.count : g.n_checks) : s.kind == 1 ? 5 * g.auth_counts[s.which] : (u64)g.W[s.which] * g.n_checks;
 }
 __global__ void __launch_bounds__(256) k_tail_gather(TailGatherArgs g) {
     __shared__ u64 offset_s;
@@ -198,8 +124,9 @@ __global__ void __launch_bounds__(256) k_tail_gather(TailGatherArgs g) {
     u64* out = g.out + offset_s;
     if (blockIdx.x == 0 && threadIdx.x == 0) g.directory[2 * seg] = offset_s, g.directory[2 * seg + 1] = words;
     for (u64 e = (u64)blockIdx.x * blockDim.x + threadIdx.x; e < words; e += (u64)gridDim.x * blockDim.x) {
-        if (s.kind == 0) {
-            out[e] = s.src[3 * ((g.a[e / 3] + s.add) & s.mask) + e % 3];
+        if (s.kind == 0) {   // element e / 3 = element `rest` of the stack at index `at`
+            const u64 stack = s.stack ? s.stack : 1, at = e / (3 * stack), rest = e / 3 % stack;
+            out[e] = s.src[3 * ((((s.idx ? s.idx : g.a)[at] + s.add) & s.mask) + rest * s.stride) + e % 3];
         } else if (s.kind == 1) {
             out[e] = s.src[5 * g.auth_idx[s.which * g.auth_stride + e / 5] + e % 5];
         } else {   // reveal_rows (k_gather_rows, hash.hip): domain row -> storage row of the row-block-major table
@@ -216,10 +143,17 @@ u32 pow2_ceil(u64 n) {
     while (p < n) p <<= 1;
     return p;
 }
-// words of an authentication structure's index list: no more than one sibling per level and path
-u64 auth_capacity(u64 n_leaves, u64 n_idx) { return std::min(n_idx, n_leaves) * (u64)ilog2(n_leaves); }
 u64 responses(u32 n_rounds) { return n_rounds ? n_rounds + 1u : 1u; }
 }  // namespace
+
+int authentication_structures_launch(tvm_ctx* c, const AuthJob* d_jobs, u32 n_jobs, u64 most_indices, u64* d_counts) {
+    TVM_LAUNCH(k_authentication_structures, dim3(n_jobs), dim3(pow2_ceil(most_indices)), 0, c->stream, d_jobs, d_counts);
+    return hipGetLastError() == hipSuccess ? TVM_OK : set_error(c, TVM_ERR_DEVICE, "authentication structures launch");
+}
+int tail_gather_launch(tvm_ctx* c, const TailGatherArgs& g, u32 n_segments) {
+    TVM_LAUNCH(k_tail_gather, dim3(16, n_segments), dim3(256), 0, c->stream, g);
+    return hipGetLastError() == hipSuccess ? TVM_OK : set_error(c, TVM_ERR_DEVICE, "tail gather launch");
+}
 
 }  // namespace tvm
 
@@ -286,8 +220,7 @@ int32_t tvm_authentication_structures(tvm_ctx* c, uint32_t n_trees, const uint64
     if (hipMemcpyAsync(d, host.data(), w_in * sizeof(u64), hipMemcpyHostToDevice, c->stream) != hipSuccess)
         rc = set_error(c, TVM_ERR_DEVICE, "authentication structures upload");
     if (rc == TVM_OK) {
-        TVM_LAUNCH(k_authentication_structures, dim3(n_trees), dim3(pow2_ceil(most)), 0, c->stream, (const AuthJob*)d, d_counts);
-        if (hipGetLastError() != hipSuccess) rc = set_error(c, TVM_ERR_DEVICE, "authentication structures launch");
+        rc = authentication_structures_launch(c, (const AuthJob*)d, n_trees, most, d_counts);
     }
     if (rc == TVM_OK && hipMemcpyAsync(back.data(), d_counts, w_back * sizeof(u64), hipMemcpyDeviceToHost, c->stream) != hipSuccess)
         rc = set_error(c, TVM_ERR_DEVICE, "authentication structures download");
@@ -383,11 +316,11 @@ int32_t tvm_fri_query_and_open(tvm_ctx* c, const uint64_t* h_state, const uint64
     st.state = d_state, st.n_indices = (u32)n_checks, st.mask = dom.length - 1, st.indices = d_a;
     st.polynomial = d_poly, st.n_coefficients = (u32)n_last, st.discriminant = 5;   // ProofItem::Polynomial (proof_item.rs: the sixth variant)
     TVM_LAUNCH(k_sponge_tail, dim3(1), dim3(64), 0, c->stream, st);
-    TVM_LAUNCH(k_authentication_structures, dim3(n_lists), dim3(pow2_ceil(n_checks)), 0, c->stream, (const AuthJob*)d, d_counts);
+    rc = authentication_structures_launch(c, (const AuthJob*)d, n_lists, n_checks, d_counts);
     tg.segments = (const TailSegment*)(d + w_jobs), tg.a = d_a, tg.auth_idx = d_auth, tg.auth_counts = d_counts;
     tg.n_checks = n_checks, tg.auth_stride = auth_stride, tg.out = d_payload, tg.directory = d_directory;
-    TVM_LAUNCH(k_tail_gather, dim3(16, n_segments), dim3(256), 0, c->stream, tg);
-    if (hipGetLastError() != hipSuccess) return leave(set_error(c, TVM_ERR_DEVICE, "tvm_fri_query_and_open launch"));
+    if (rc == TVM_OK) rc = tail_gather_launch(c, tg, n_segments);
+    if (rc != TVM_OK) return leave(rc);   // (a refused launch of the sponge shows in the next launch's check)
 
     // first round trip: what has a fixed size
     if (hipMemcpyAsync(fixed.data(), d_fixed, w_fixed * sizeof(u64), hipMemcpyDeviceToHost, c->stream) != hipSuccess ||

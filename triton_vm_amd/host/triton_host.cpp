@@ -938,9 +938,97 @@ Stir Stir::for_stark(u64 padded_height, unsigned security_level, unsigned log2_e
     throw Error(TVM_ERR_INVALID_ARGUMENT, "no suitable STIR parameters found");
 }
 
+namespace {
+std::vector<u64> unique_folded(const std::vector<u64>& indices, u64 folded_len) {  // .map(|i| i % len).unique()
+    std::vector<u64> out;
+    for (u64 i : indices) {
+        const u64 f = i % folded_len;
+        if (std::find(out.begin(), out.end(), f) == out.end()) out.push_back(f);
+    }
+    return out;
+}
+}  // namespace
+
+static std::atomic<uint64_t> g_device_stir_proofs{0};   // tvmh_device_stir_proofs
+// TVMH_OPTION_DEVICE_STIR: the whole of Stir::prove in one call, the sponge on the device (tvm_stir_prove_rounds: two stream
+// synchronisations, no host work between the rounds) -- then every enqueue and every sampling is replayed on this host's sponge, which
+// must arrive at the same scalars, the same indices and the same state.  false: the call does not apply (a round with more than
+// TVM_TAIL_MAX_INDICES in-domain queries, or a full round with more than 256 queries in all) and nothing was enqueued.
+bool Stir::prove_on_device(const Context& c, const u64* d_codeword, ProofStream& ps, std::vector<u64>& first_round_indices) const {
+    const uint32_t R = (uint32_t)round_queries.size();
+    std::vector<u64> pairs, queries;
+    u64 n_ood_all = 0, n_queries_all = final_num_in_domain_queries, n_final = initial_domain.length;
+    for (const auto& q : round_queries) {
+        pairs.push_back(q.first), pairs.push_back(q.second), queries.push_back(q.first);
+        n_ood_all += q.second, n_queries_all += q.first;
+    }
+    queries.push_back(final_num_in_domain_queries);
+    for (uint32_t r = 0; r <= R; r++) n_final = (n_final + folding_factor - 1) / folding_factor;
+    const u64 capacity = tvm_stir_prove_rounds_payload_bound(initial_domain.c(), (uint32_t)folding_factor, R, pairs.data(), final_num_in_domain_queries);
+    u64 state[16], n_payload = 0;
+    std::vector<u64> roots(5 * ((size_t)R + 1)), indices(n_queries_all), unique(n_queries_all), unique_counts((size_t)R + 1), final_words(3 * n_final),
+        directory(4 * ((size_t)R + 1)), ood_values(3 * n_ood_all + 1);
+    std::vector<Xfe> scalars(2 * (size_t)R + 1 + n_ood_all);
+    // (room for the bound -- every index distinct, full paths -- but not filled: only the pages the proof's words reach are touched)
+    const std::unique_ptr<u64[]> payload(new u64[capacity ? capacity : 1]);
+    const int32_t status = tvm_stir_prove_rounds(c.raw(), ps.sponge_state(), d_codeword, initial_domain.c(), (uint32_t)folding_factor, R, pairs.data(),
+                                                 final_num_in_domain_queries, final_degree, state, roots.data(), scalars[0].c, ood_values.data(),
+                                                 indices.data(), unique.data(), unique_counts.data(), final_words.data(), directory.data(),
+                                                 payload.get(), capacity, &n_payload);
+    if (status == TVM_NOT_APPLICABLE) return false;
+    c.check(status, "tvm_stir_prove_rounds");
+    auto agree = [](bool same, const char* what) {
+        if (!same) throw Error(TVM_ERR_DEVICE, std::string("the device's Fiat-Shamir sponge and the host's disagree on ") + what);
+    };
+    auto same_scalars = [&](const std::vector<Xfe>& mine, const Xfe* theirs) {
+        return mine.empty() || std::memcmp(mine[0].c, theirs->c, mine.size() * sizeof(Xfe)) == 0;
+    };
+    // tree t's response: the indices the host samples must be the device's, and their first occurrences mod the folded length its list
+    const Xfe* scalar = scalars.data();
+    const u64 *raw = indices.data(), *list = unique.data();
+    ArithmeticDomain domain = initial_domain;
+    auto respond = [&](uint32_t t) {
+        const std::vector<u64> queried = ps.sample_indices(domain.length, queries[t]);
+        agree(std::equal(queried.begin(), queried.end(), raw), "the STIR query indices");
+        const std::vector<u64> folded = unique_folded(queried, domain.length / folding_factor);
+        agree(folded.size() == unique_counts[t] && std::equal(folded.begin(), folded.end(), list), "the STIR query indices without repeats");
+        ps.enqueue("stir response leafs", payload.get() + directory[4 * t], directory[4 * t + 1], folding_factor * 3);
+        ps.enqueue("stir response auth", payload.get() + directory[4 * t + 2], directory[4 * t + 3]);
+        raw += queries[t], list += queries[t];
+        return queried;
+    };
+    ps.enqueue("stir root", roots.data(), 5);
+    const u64* values = ood_values.data();
+    for (uint32_t r = 0; r < R; r++) {
+        const u64 n_ood = round_queries[r].second;
+        agree(same_scalars(ps.sample_scalars(1), scalar), "a STIR folding randomness");
+        ps.enqueue("stir root", roots.data() + 5 * ((size_t)r + 1), 5);
+        agree(same_scalars(ps.sample_scalars(n_ood), scalar + 1), "the STIR out-of-domain points");
+        ps.enqueue("stir ood values", n_ood ? values : nullptr, 3 * n_ood);
+        const std::vector<u64> queried = respond(r);
+        if (r == 0) first_round_indices = queried;
+        agree(same_scalars(ps.sample_scalars(1), scalar + 1 + n_ood), "a STIR degree-correction randomness");
+        scalar += 2 + n_ood, values += 3 * n_ood;
+        ArithmeticDomain next = domain.pow(1ull << LOG2_DOMAIN_SHRINKAGE);
+        domain = next.with_offset(mont_mul(next.offset, domain.offset));
+    }
+    agree(same_scalars(ps.sample_scalars(1), scalar), "the final STIR folding randomness");
+    ps.enqueue("stir final polynomial", final_words.data(), final_words.size());
+    const std::vector<u64> queried = respond(R);
+    if (R == 0) first_round_indices = queried;
+    agree(std::memcmp(state, ps.sponge_state(), sizeof(state)) == 0, "the state after STIR");
+    g_device_stir_proofs++;
+    return true;
+}
+
 // Stir::prove (stir.rs:885-993).  Device work through the C ABI: stacked Merkle trees, polynomial folding, the witness
-// polynomial of the next round, the answer polynomial (tvm_xfe_interpolate); host: sampling, inclusion proofs.
+// polynomial of the next round, the answer polynomial (tvm_xfe_interpolate); host: sampling, inclusion proofs.  Under
+// TVMH_OPTION_DEVICE_STIR the rounds run on the device where that applies (prove_on_device), the same items word for word.
 std::vector<u64> Stir::prove(const Context& c, const u64* d_codeword, ProofStream& ps) const {
+    if (tvmh_get_option(TVMH_OPTION_DEVICE_STIR)) {
+        std::vector<u64> first_round_indices;
+        if (prove_on_device(c, d_codeword, ps, first_round_indices)) return first_round_indices;
+    }
     const u64 ff = folding_factor;
     struct Commitment {
         const u64* codeword;
@@ -963,14 +1051,6 @@ std::vector<u64> Stir::prove(const Context& c, const u64* d_codeword, ProofStrea
         ps.enqueue("stir response leafs", leafs.data(), leafs.size(), ff * 3);
         const std::vector<u64> auth = auth_nodes(c, t.nodes, t.n_leaves, folded_indices);
         ps.enqueue("stir response auth", auth.data(), auth.size());
-    };
-    auto unique_folded = [](const std::vector<u64>& indices, u64 folded_len) {  // .map(|i| i % len).unique()
-        std::vector<u64> out;
-        for (u64 i : indices) {
-            const u64 f = i % folded_len;
-            if (std::find(out.begin(), out.end(), f) == out.end()) out.push_back(f);
-        }
-        return out;
     };
     auto fold = [&](const u64* poly, u64 n_coeffs, const Xfe& randomness, u64* n_out) {
         *n_out = (n_coeffs + ff - 1) / ff;
@@ -1197,13 +1277,14 @@ std::vector<u64> prove_execution(const Context& c, const StarkParameters& p, con
 
 }  // namespace triton_vm
 
-static std::atomic<uint64_t> g_options[7] = {{0}, {0}, {0}, {0}, {0}, {0}, {0}};   // indexed by TVMH_OPTION_*
+static std::atomic<uint64_t> g_options[8] = {{0}, {0}, {0}, {0}, {0}, {0}, {0}, {0}};   // indexed by TVMH_OPTION_*
 extern "C" void tvmh_set_option(uint32_t option, uint64_t value) {
-    if (option >= 1 && option <= 6) g_options[option].store(value);
+    if (option >= 1 && option <= 7) g_options[option].store(value);
 }
-extern "C" uint64_t tvmh_get_option(uint32_t option) { return option >= 1 && option <= 6 ? g_options[option].load() : 0; }
+extern "C" uint64_t tvmh_get_option(uint32_t option) { return option >= 1 && option <= 7 ? g_options[option].load() : 0; }
 
 extern "C" uint64_t tvmh_device_tail_proofs(void) { return triton_vm::g_device_tail_proofs.load(); }
+extern "C" uint64_t tvmh_device_stir_proofs(void) { return triton_vm::g_device_stir_proofs.load(); }
 
 extern "C" int32_t tvmh_prove(tvm_ctx* ctx, uint32_t log2_padded_height, uint64_t num_trace_randomizers,
                               uint64_t num_collinearity_checks, uint32_t log2_expansion, const uint64_t* d_main_trace,

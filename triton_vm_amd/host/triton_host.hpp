@@ -173,6 +173,9 @@ struct Stir {
     static Stir for_stark(u64 padded_height, unsigned security_level, unsigned log2_expansion);
     // Stir::prove: enqueues roots, out-of-domain values, responses and the final polynomial; -> first-round indices
     std::vector<u64> prove(const Context& c, const u64* d_codeword, ProofStream& ps) const;
+    // the same with the rounds and the sponge on the device (TVMH_OPTION_DEVICE_STIR); false, and nothing enqueued, where
+    // tvm_stir_prove_rounds does not apply to the instance
+    bool prove_on_device(const Context& c, const u64* d_codeword, ProofStream& ps, std::vector<u64>& first_round_indices) const;
 };
 
 // Domains for a padded height as Stark::default() with LdtChoice::Fri derives them
@@ -522,6 +525,15 @@ extern "C" int32_t tvmh_check_execution(tvm_ctx* ctx, const tvm_aet* aet, uint32
 #define TVMH_OPTION_DEVICE_TAIL 6
 // how many proofs of this process took that path so far (a proof it does not apply to is not counted: tests and the timing tool ask)
 extern "C" uint64_t tvmh_device_tail_proofs(void);
+// TVMH_OPTION_DEVICE_STIR != 0: Stir::prove -- wherever it is called: the single-GPU, the sharded and the coset-wise prover, tvmh_stir_prove --
+// runs all its rounds in one call with the sponge on the device (tvm_stir_prove_rounds: two stream synchronisations instead of about six
+// per round, no host work between the rounds); the host replays every enqueue and every sampling on its own sponge and throws
+// TVM_ERR_DEVICE when a scalar, an index list or the state differs.  The same proof, word for word.  Default 0.  An instance with a round
+// of more than TVM_TAIL_MAX_INDICES in-domain queries or a full round of more than 256 queries in all (TVM_NOT_APPLICABLE) keeps the host's loop whatever
+// the value; the trace openings of a STIR proof stay on the host's path.
+#define TVMH_OPTION_DEVICE_STIR 7
+// how many calls of Stir::prove in this process took that path so far (one it does not apply to is not counted)
+extern "C" uint64_t tvmh_device_stir_proofs(void);
 extern "C" void tvmh_set_option(uint32_t option, uint64_t value);
 extern "C" uint64_t tvmh_get_option(uint32_t option);
 

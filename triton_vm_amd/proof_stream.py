@@ -317,6 +317,8 @@ class ProofStream:
         return out
 
     def sample_scalars(self, n):
+        if n == 0:   # (proof_stream.rs:81-84: no squeeze; STIR samples its out-of-domain points this way when a round has none)
+            return np.zeros((0, 3), np.uint64)
         words = np.concatenate([self._squeeze() for _ in range((3 * n + 9) // 10)])
         return words[:3 * n].reshape(n, 3)
 

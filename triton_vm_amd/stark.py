@@ -108,6 +108,8 @@ def quotient_segments_from_coefficients(ctx, d_coeffs, n_coeffs, ldt_domain, ran
 def evaluate_at_points(ctx, d_coeffs, n, points):
     pts = _h(points).reshape(-1, 3)
     out = np.empty((pts.shape[0], 3), np.uint64)
+    if not pts.shape[0]:   # (the entry point refuses an empty list of points)
+        return out
     ctx._check(ctx.lib.tvm_evaluate_at_points(ctx.handle, d_coeffs.ptr, n, pts.ctypes.data, pts.shape[0], out.ctypes.data),
                "evaluate_at_points")
     return out
