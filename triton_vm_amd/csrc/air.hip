@@ -155,27 +155,6 @@ __global__ void __launch_bounds__(256) k_air_scatter_tiles(AirArgs a, const u64*
 
 bool air_parts_fork(const tvm_ctx* c, u64 q_len) { return (q_len + AIR_BLOCK - 1) / AIR_BLOCK <= c->air_fork_max_workgroups; }
 
-bool fork_lanes(tvm_ctx* c) {
-    if (c->fork_ready) return true;
-    int cur = -1;   // streams belong to the device that is current when they are created
-    if ((hipGetDevice(&cur) != hipSuccess || cur != c->device) && hipSetDevice(c->device) != hipSuccess) return false;
-    hipStream_t s[3] = {};
-    hipEvent_t e[4] = {};
-    bool ok = true;
-    for (int k = 0; k < 3 && ok; k++) ok = hipStreamCreateWithFlags(&s[k], hipStreamNonBlocking) == hipSuccess;
-    for (int k = 0; k < 4 && ok; k++) ok = hipEventCreateWithFlags(&e[k], hipEventDisableTiming) == hipSuccess;
-    if (!ok) {
-        for (hipStream_t x : s)
-            if (x) hipStreamDestroy(x);
-        for (hipEvent_t x : e)
-            if (x) hipEventDestroy(x);
-        return false;
-    }
-    for (int k = 0; k < 3; k++) c->fork[k] = s[k], c->fork_done[k] = e[k];
-    c->fork_ready = e[3];
-    return true;
-}
-
 static int air_run(tvm_ctx* c, AirArgs a, u64 trace_len, u64 trace_gen, u64 q_offset, u64 q_gen, u64 index_step,
                    const u64* d_challenges, const u64* d_weights, u64* d_out, int part_select, int accumulate,
                    const u64* d_zinv = nullptr);
@@ -278,8 +257,8 @@ static int air_run(tvm_ctx* c, AirArgs a, u64 trace_len, u64 trace_gen, u64 q_of
         if (!part_select || (part_select >> TVM_AIR_PART_CLASS[p] & 1)) selected[n_selected++] = p;
     int n_lanes = 1;
     if (n_selected > 1 && air_parts_fork(c, q_len) && fork_lanes(c)) n_lanes = n_selected < 4 ? n_selected : 4;
-    u64* zinv = d_zinv ? nullptr : (u64*)scratch(c, 14, (size_t)4 * q_len * sizeof(u64));
-    u64* acc = (u64*)scratch(c, 23, (size_t)n_lanes * 3 * q_len * sizeof(u64));
+    u64* zinv = d_zinv ? nullptr : (u64*)scratch(c, Scratch::ZerofierInverses, (size_t)4 * q_len * sizeof(u64));
+    u64* acc = (u64*)scratch(c, Scratch::AirAccumulators, (size_t)n_lanes * 3 * q_len * sizeof(u64));
     if ((!d_zinv && !zinv) || !acc) return set_error(c, TVM_ERR_OUT_OF_MEMORY, "zerofier inverses");
     a.challenges = d_challenges;
     a.weights = d_weights;

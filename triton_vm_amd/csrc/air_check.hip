@@ -142,12 +142,12 @@ extern "C" int32_t tvm_check_constraints(tvm_ctx* c, const uint64_t* d_main_trac
     static const uint8_t fixed_seed[32] = {0};
     std::vector<u64> weights(3 * TVM_NUM_QUOTIENT_WEIGHTS);
     tvm_host_stdrng_elements(seed ? seed : fixed_seed, weights.size(), weights.data());
-    u64* staged = (u64*)scratch(c, 28, (size_t)3 * (TVM_NUM_CHALLENGES + TVM_NUM_QUOTIENT_WEIGHTS) * sizeof(u64));
-    u64* sel = (u64*)scratch(c, 29, (size_t)4 * R * sizeof(u64));
-    u64* vals = (u64*)scratch(c, 30, (size_t)3 * R * sizeof(u64));
-    u64* offsets = (u64*)scratch(c, 31, (size_t)(groups + 1) * sizeof(u64));   // [groups] offsets, then the running total
-    u32* counts = (u32*)scratch(c, 32, (size_t)groups * sizeof(u32));
-    u64* listed = (u64*)scratch(c, 33, (size_t)(listed_cap ? listed_cap : 1) * sizeof(u64));
+    u64* staged = (u64*)scratch(c, Scratch::AirCheckInputs, (size_t)3 * (TVM_NUM_CHALLENGES + TVM_NUM_QUOTIENT_WEIGHTS) * sizeof(u64));
+    u64* sel = (u64*)scratch(c, Scratch::AirCheckSelectors, (size_t)4 * R * sizeof(u64));
+    u64* vals = (u64*)scratch(c, Scratch::AirCheckValues, (size_t)3 * R * sizeof(u64));
+    u64* offsets = (u64*)scratch(c, Scratch::AirCheckOffsets, (size_t)(groups + 1) * sizeof(u64));   // [groups] offsets, then the running total
+    u32* counts = (u32*)scratch(c, Scratch::AirCheckCounts, (size_t)groups * sizeof(u32));
+    u64* listed = (u64*)scratch(c, Scratch::AirCheckListed, (size_t)(listed_cap ? listed_cap : 1) * sizeof(u64));
     if (!staged || !sel || !vals || !offsets || !counts || !listed) return set_error(c, TVM_ERR_OUT_OF_MEMORY, "constraint check scratch");
     u64* total = offsets + groups;
     TVM_TRY(h2d_small(c, staged, h_challenges, 3 * TVM_NUM_CHALLENGES * sizeof(u64)));
@@ -186,8 +186,8 @@ extern "C" int32_t tvm_check_constraints(tvm_ctx* c, const uint64_t* d_main_trac
     // pinpoint: rows r and r + 1 of each listed row, all 604 constraints on the host, the applicable non-zero ones reported
     constexpr u64 RW = CHECK_MAIN_W + CHECK_AUX_W;
     const u64 batch = k < CHECK_BATCH ? k : CHECK_BATCH;
-    u64* d_idx = (u64*)scratch(c, 34, (size_t)2 * batch * sizeof(u64));
-    u64* d_pairs = (u64*)scratch(c, 35, (size_t)2 * batch * RW * sizeof(u64));
+    u64* d_idx = (u64*)scratch(c, Scratch::AirCheckPairIndices, (size_t)2 * batch * sizeof(u64));
+    u64* d_pairs = (u64*)scratch(c, Scratch::AirCheckPairs, (size_t)2 * batch * RW * sizeof(u64));
     if (!d_idx || !d_pairs) return set_error(c, TVM_ERR_OUT_OF_MEMORY, "constraint check rows");
     std::vector<u64> idx(2 * batch), pairs(2 * batch * RW), main_cur(3 * TVM_NUM_MAIN_COLUMNS, 0), main_next(3 * TVM_NUM_MAIN_COLUMNS, 0),
         values(3 * TVM_NUM_QUOTIENT_WEIGHTS);

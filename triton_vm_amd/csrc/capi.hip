@@ -1,5 +1,6 @@
-// capi.hip -- the extern "C" boundary of libtriton_hip.so (declared in include/triton_hip.h).
-// Argument validation and error mapping live here; kernels live in ntt.hip / hash.hip / poly.hip.
+// capi.hip -- the extern "C" boundary of libtriton_hip.so (declared in include/triton_hip.h), the context's own entry points
+// apart (context.hip).  Argument validation and error mapping live here, and the small kernels that belong to no unit of their own
+// (synthetic data, the field self-check, folds, combinations, gathers); the large ones live in ntt.hip / hash.hip / poly.hip / air.hip.
 #include <cstring>
 #include <new>
 #include <vector>
@@ -9,252 +10,8 @@
 
 using namespace tvm;
 
-#define TVM_ABI_VERSION 1
-
 static bool valid_fk(int32_t fk) { return fk == 1 || fk == 3; }
 static bool valid_domain(const tvm_domain& d) { return is_pow2(d.length) && d.length >= 1 && d.generator < TVM_P && d.offset < TVM_P; }
-
-extern "C" {
-
-int32_t tvm_abi_version(void) { return TVM_ABI_VERSION; }
-
-const char* tvm_status_string(int32_t s) {
-    switch (s) {
-        case TVM_OK: return "ok";
-        case TVM_ERR_INVALID_ARGUMENT: return "invalid argument";
-        case TVM_ERR_OUT_OF_MEMORY: return "device out of memory";
-        case TVM_ERR_DEVICE: return "HIP runtime error";
-        case TVM_ERR_UNSUPPORTED: return "unsupported size or configuration";
-        case TVM_NOT_APPLICABLE: return "not applicable to these arguments";
-        default: return "unknown status";
-    }
-}
-
-int32_t tvm_ctx_create(int32_t device, void* hip_stream, tvm_ctx** out) {
-    if (!out) return TVM_ERR_INVALID_ARGUMENT;
-    *out = nullptr;
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || count <= 0 || device < 0 || device >= count) return TVM_ERR_DEVICE;
-    if (hipSetDevice(device) != hipSuccess) return TVM_ERR_DEVICE;
-    tvm_ctx* c = new (std::nothrow) tvm_ctx();
-    if (!c) return TVM_ERR_OUT_OF_MEMORY;
-    c->device = device;
-    if (hip_stream) {
-        c->stream = (hipStream_t)hip_stream;
-    } else {
-        if (hipStreamCreate(&c->stream) != hipSuccess) {
-            delete c;
-            return TVM_ERR_DEVICE;
-        }
-        c->owns_stream = true;
-    }
-    *out = c;
-    return TVM_OK;
-}
-
-void tvm_ctx_destroy(tvm_ctx* c) {
-    if (!c) return;
-    hipStreamSynchronize(c->stream);
-    for (auto& kv : c->tables) hipFree(kv.second);
-    for (void* p : c->scratch)
-        if (p) hipFree(p);
-    for (auto& kv : c->pool_free) hipFree(kv.second);
-    for (auto& kv : c->pool_live) hipFree(kv.first);
-    if (c->ev_start) hipEventDestroy(c->ev_start);
-    if (c->ev_stop) hipEventDestroy(c->ev_stop);
-    if (c->side) {
-        hipStreamSynchronize(c->side);
-        hipStreamDestroy(c->side);
-    }
-    if (c->side_ready) hipEventDestroy(c->side_ready);
-    for (hipStream_t s : c->fork)
-        if (s) {
-            hipStreamSynchronize(s);
-            hipStreamDestroy(s);
-        }
-    if (c->fork_ready) hipEventDestroy(c->fork_ready);
-    for (hipEvent_t e : c->fork_done)
-        if (e) hipEventDestroy(e);
-    for (hipEvent_t e : c->side_done)
-        if (e) hipEventDestroy(e);
-    if (c->pin) hipHostFree(c->pin);
-    if (c->owns_stream) hipStreamDestroy(c->stream);
-    delete c;
-}
-
-const char* tvm_last_error(const tvm_ctx* c) { return c ? c->last_error.c_str() : "null context"; }
-
-int32_t tvm_sync(tvm_ctx* c) {
-    if (!c) return TVM_ERR_INVALID_ARGUMENT;
-    TVM_HIP_CHECK(c, hipStreamSynchronize(c->stream));
-    return TVM_OK;
-}
-int32_t tvm_malloc(tvm_ctx* c, size_t bytes, void** d_ptr) {
-    if (!c || !d_ptr) return TVM_ERR_INVALID_ARGUMENT;
-    *d_ptr = pool_alloc(c, bytes);
-    if (!*d_ptr) return set_error(c, TVM_ERR_OUT_OF_MEMORY, "tvm_malloc");
-    return TVM_OK;
-}
-int32_t tvm_free(tvm_ctx* c, void* d_ptr) {
-    if (!c) return TVM_ERR_INVALID_ARGUMENT;
-    pool_release(c, d_ptr);
-    return TVM_OK;
-}
-int32_t tvm_ctx_set_memory_limit(tvm_ctx* c, size_t bytes) {
-    if (!c) return TVM_ERR_INVALID_ARGUMENT;
-    c->pool_limit = bytes;
-    return TVM_OK;
-}
-int32_t tvm_ctx_memory_held(const tvm_ctx* c, size_t* bytes) {
-    if (!c || !bytes) return TVM_ERR_INVALID_ARGUMENT;
-    *bytes = c->pool_bytes;
-    return TVM_OK;
-}
-int32_t tvm_ctx_memory_info(const tvm_ctx* c, size_t* available_bytes, size_t* device_total_bytes) {
-    if (!c) return TVM_ERR_INVALID_ARGUMENT;
-    int cur = -1;
-    (void)hipGetDevice(&cur);
-    size_t total = 0;
-    const size_t avail = pool_available(const_cast<tvm_ctx*>(c), &total);   // (binds the context's device; reads the pool only)
-    if (cur >= 0 && cur != c->device) (void)hipSetDevice(cur);
-    if (!total) return TVM_ERR_DEVICE;
-    if (available_bytes) *available_bytes = avail;
-    if (device_total_bytes) *device_total_bytes = total;
-    return TVM_OK;
-}
-int32_t tvm_ctx_set_option(tvm_ctx* c, int32_t option, uint64_t value) {
-    if (!c) return TVM_ERR_INVALID_ARGUMENT;
-    if (option == TVM_OPTION_AIR_VALID_TRACE) {
-        c->air_valid_trace = value != 0;
-        return TVM_OK;
-    }
-    if (option == TVM_OPTION_LDE_CHUNK_COLUMNS) {
-        if (value > 4096) return set_error(c, TVM_ERR_INVALID_ARGUMENT, "TVM_OPTION_LDE_CHUNK_COLUMNS: at most 4096");
-        c->lde_chunk_columns = (int)value;
-        return TVM_OK;
-    }
-    if (option == TVM_OPTION_LDE_PASS2_TILES) {
-        c->lde_pass2_tiles = value ? 1 : 0;
-        return TVM_OK;
-    }
-    if (option == TVM_OPTION_MERKLE_SUBTREES) {
-        c->merkle_subtrees = value != 0;
-        return TVM_OK;
-    }
-    if (option == TVM_OPTION_AIR_FORK_MAX_WORKGROUPS) {
-        c->air_fork_max_workgroups = value;
-        return TVM_OK;
-    }
-    if (option == TVM_OPTION_AIR_REMAINDER_COSET) {
-        c->air_remainder_coset = value != 0;
-        return TVM_OK;
-    }
-    if (option == TVM_OPTION_AIR_REMAINDER_MIN_ROWS) {
-        c->air_remainder_min_rows = value ? value : 1ull << 18;
-        return TVM_OK;
-    }
-    if (option == TVM_OPTION_AIR_CHECK_CHUNK_ROWS) {
-        if (value && (!is_pow2(value) || value < TVM_RB || value > (1ull << 20)))
-            return set_error(c, TVM_ERR_INVALID_ARGUMENT, "TVM_OPTION_AIR_CHECK_CHUNK_ROWS: a power of two in 16 .. 2^20");
-        c->air_check_chunk_rows = value ? value : 1ull << 18;
-        return TVM_OK;
-    }
-    if (option == TVM_OPTION_MERKLE_MIN_WORKGROUPS) {
-        c->merkle_min_workgroups = value ? value : 4096;
-        return TVM_OK;
-    }
-    return set_error(c, TVM_ERR_INVALID_ARGUMENT, "unknown option");
-}
-int32_t tvm_ctx_trim(tvm_ctx* c) {
-    if (!c) return TVM_ERR_INVALID_ARGUMENT;
-    pool_trim(c);
-    return TVM_OK;
-}
-int32_t tvm_memcpy_h2d(tvm_ctx* c, void* d, const void* h, size_t bytes) {
-    if (!c || (bytes && (!d || !h))) return TVM_ERR_INVALID_ARGUMENT;
-    TVM_HIP_CHECK(c, hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, c->stream));
-    TVM_HIP_CHECK(c, hipStreamSynchronize(c->stream));
-    return TVM_OK;
-}
-int32_t tvm_memcpy_d2h(tvm_ctx* c, void* h, const void* d, size_t bytes) {
-    if (!c || (bytes && (!d || !h))) return TVM_ERR_INVALID_ARGUMENT;
-    TVM_HIP_CHECK(c, hipMemcpyAsync(h, d, bytes, hipMemcpyDeviceToHost, c->stream));
-    TVM_HIP_CHECK(c, hipStreamSynchronize(c->stream));
-    return TVM_OK;
-}
-int32_t tvm_memcpy_d2d(tvm_ctx* c, void* dst, const void* src, size_t bytes) {
-    if (!c || (bytes && (!dst || !src))) return TVM_ERR_INVALID_ARGUMENT;
-    if (bytes) TVM_HIP_CHECK(c, hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, c->stream));
-    return TVM_OK;
-}
-void* tvm_ctx_stream(const tvm_ctx* c) { return c ? (void*)c->stream : nullptr; }
-
-// ---- the side lane (include/triton_hip.h)
-static_assert(TVM_SIDE_SLOTS == 16, "tvm_ctx::side_done has sixteen slots");
-static bool side_lane(tvm_ctx* c) {
-    if (c->side) return true;
-    int cur = -1;   // streams belong to the device that is current when they are created (see bind_device, ntt.hip)
-    if ((hipGetDevice(&cur) != hipSuccess || cur != c->device) && hipSetDevice(c->device) != hipSuccess) return false;
-    hipStream_t s = nullptr;
-    hipEvent_t ready = nullptr;
-    if (hipStreamCreateWithFlags(&s, hipStreamNonBlocking) != hipSuccess) return false;
-    if (hipEventCreateWithFlags(&ready, hipEventDisableTiming) != hipSuccess) {
-        hipStreamDestroy(s);
-        return false;
-    }
-    c->side = s;
-    c->side_ready = ready;
-    return true;
-}
-void* tvm_ctx_side_stream(tvm_ctx* c) { return c && side_lane(c) ? (void*)c->side : nullptr; }
-int32_t tvm_side_begin(tvm_ctx* c) {
-    if (!c) return TVM_ERR_INVALID_ARGUMENT;
-    if (!side_lane(c)) return tvm::set_error(c, TVM_ERR_DEVICE, "tvm_side_begin: no second stream");
-    TVM_HIP_CHECK(c, hipEventRecord(c->side_ready, c->stream));
-    TVM_HIP_CHECK(c, hipStreamWaitEvent(c->side, c->side_ready, 0));
-    return TVM_OK;
-}
-int32_t tvm_side_memcpy_d2d(tvm_ctx* c, void* dst, const void* src, size_t bytes) {
-    if (!c || (bytes && (!dst || !src))) return TVM_ERR_INVALID_ARGUMENT;
-    if (!side_lane(c)) return tvm::set_error(c, TVM_ERR_DEVICE, "tvm_side_memcpy_d2d: no second stream");
-    if (bytes) TVM_HIP_CHECK(c, hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, c->side));
-    return TVM_OK;
-}
-int32_t tvm_side_mark(tvm_ctx* c, uint32_t slot) {
-    if (!c || slot >= TVM_SIDE_SLOTS) return TVM_ERR_INVALID_ARGUMENT;
-    if (!side_lane(c)) return tvm::set_error(c, TVM_ERR_DEVICE, "tvm_side_mark: no second stream");
-    if (!c->side_done[slot]) TVM_HIP_CHECK(c, hipEventCreateWithFlags(&c->side_done[slot], hipEventDisableTiming));
-    TVM_HIP_CHECK(c, hipEventRecord(c->side_done[slot], c->side));
-    return TVM_OK;
-}
-int32_t tvm_side_wait(tvm_ctx* c, uint32_t slot) {
-    if (!c || slot >= TVM_SIDE_SLOTS) return TVM_ERR_INVALID_ARGUMENT;
-    if (c->side_done[slot]) TVM_HIP_CHECK(c, hipStreamWaitEvent(c->stream, c->side_done[slot], 0));   // (never marked: nothing to wait for)
-    return TVM_OK;
-}
-int32_t tvm_side_sync(tvm_ctx* c) {
-    if (!c) return TVM_ERR_INVALID_ARGUMENT;
-    if (c->side) TVM_HIP_CHECK(c, hipStreamSynchronize(c->side));
-    return TVM_OK;
-}
-
-int32_t tvm_timer_start(tvm_ctx* c) {
-    if (!c) return TVM_ERR_INVALID_ARGUMENT;
-    if (!c->ev_start) {
-        TVM_HIP_CHECK(c, hipEventCreate(&c->ev_start));
-        TVM_HIP_CHECK(c, hipEventCreate(&c->ev_stop));
-    }
-    TVM_HIP_CHECK(c, hipEventRecord(c->ev_start, c->stream));
-    return TVM_OK;
-}
-int32_t tvm_timer_stop(tvm_ctx* c, float* ms) {
-    if (!c || !ms || !c->ev_start) return TVM_ERR_INVALID_ARGUMENT;
-    TVM_HIP_CHECK(c, hipEventRecord(c->ev_stop, c->stream));
-    TVM_HIP_CHECK(c, hipEventSynchronize(c->ev_stop));
-    TVM_HIP_CHECK(c, hipEventElapsedTime(ms, c->ev_start, c->ev_stop));
-    return TVM_OK;
-}
-}  // extern "C"
 
 namespace tvm {
 // splitmix64 of (seed, index), reduced into [0, p): synthetic benchmark data only
@@ -403,7 +160,7 @@ int32_t tvm_evaluate(tvm_ctx* c, int32_t fk, const uint64_t* d_coeffs, uint64_t 
     }
     const u64* co = d_coeffs;
     if (n_coeffs > L) {
-        u64* folded = (u64*)scratch(c, 3, L * fk * sizeof(u64));
+        u64* folded = (u64*)scratch(c, Scratch::FoldedCoefficients, L * fk * sizeof(u64));
         if (!folded) return set_error(c, TVM_ERR_OUT_OF_MEMORY, "evaluate scratch");
         const u64 total = L * fk;
         TVM_LAUNCH(k_fold_chunks, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, c->stream, d_coeffs, n_coeffs,
@@ -582,8 +339,8 @@ int32_t tvm_table_reveal_rows(tvm_ctx* c, const tvm_table* t, uint64_t ldt_lengt
         if (h_idx[j] >= ldt_length) return set_error(c, TVM_ERR_INVALID_ARGUMENT, "reveal_rows: index out of range");
         idx[j] = h_idx[j] * stride;
     }
-    u64* d_idx = (u64*)scratch(c, 4, n * sizeof(u64));
-    u64* d_out = (u64*)scratch(c, 5, n * t->W * sizeof(u64));
+    u64* d_idx = (u64*)scratch(c, Scratch::GatherIndices, n * sizeof(u64));
+    u64* d_out = (u64*)scratch(c, Scratch::GatherOut, n * t->W * sizeof(u64));
     if (!d_idx || !d_out) return set_error(c, TVM_ERR_OUT_OF_MEMORY, "reveal scratch");
     TVM_TRY(h2d_small(c, d_idx, idx.data(), n * sizeof(u64)));   // (idx is a local)
     TVM_TRY(gather_rows(c, t->data, t->layout, t->W, d_idx, n, d_out));
@@ -631,13 +388,6 @@ extern "C" int32_t tvm_codeword_merkle_tree(tvm_ctx* c, const uint64_t* d_cw, ui
 
 // ---------------------------------------------------------------------------------- combination / DEEP / FRI
 namespace tvm {
-// small host arrays (points, weights) staged into a context scratch slot
-static const u64* stage_small(tvm_ctx* c, int slot, const u64* h, size_t words) {
-    u64* d = (u64*)scratch(c, slot, (words ? words : 1) * sizeof(u64));
-    if (!d) return nullptr;
-    if (h2d_small(c, d, h, words * sizeof(u64)) != TVM_OK) return nullptr;   // (h may be a caller temporary)
-    return d;
-}
 // coeffs[i + N * r] += sum_k w[3 * r + k] * q[k][i]  (r, k < 3; i < N; XFE vectors q, base-field weights w): the polynomial
 // A + X^N B + X^2N C from its restrictions Q_k = A + c_k B + c_k^2 C to three cosets (w = the inverse Vandermonde matrix)
 struct ThreeCosetWeights {
@@ -770,8 +520,8 @@ int32_t tvm_out_of_domain_rows(tvm_ctx* c, int32_t fk, const uint64_t* d_trace, 
         !n_points || !n_cols)
         return set_error(c, TVM_ERR_INVALID_ARGUMENT, "out_of_domain_rows arguments");
     if (td.offset != TVM_ONE) return set_error(c, TVM_ERR_UNSUPPORTED, "trace domain offset must be 1");
-    const u64* d_points = stage_small(c, 9, h_points, 3 * (size_t)n_points);
-    u64* d_rows = (u64*)scratch(c, 10, (size_t)n_points * n_cols * 3 * sizeof(u64));
+    const u64* d_points = stage_small(c, Scratch::SmallIn, h_points, 3 * (size_t)n_points);
+    u64* d_rows = (u64*)scratch(c, Scratch::SmallOut, (size_t)n_points * n_cols * 3 * sizeof(u64));
     if (!d_points || !d_rows) return set_error(c, TVM_ERR_OUT_OF_MEMORY, "ood staging");
     TVM_TRY(out_of_domain_rows(c, fk, d_trace, n, n_cols, d_rnd, h, td.generator, d_points, (int)n_points, d_rows));
     TVM_HIP_CHECK(c, hipMemcpyAsync(h_rows, d_rows, (size_t)n_points * n_cols * 3 * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
@@ -786,7 +536,7 @@ int32_t tvm_weighted_sum_of_columns(tvm_ctx* c, int32_t fk, const uint64_t* d_tr
         !n_cols || h > n)
         return set_error(c, TVM_ERR_INVALID_ARGUMENT, "weighted_sum_of_columns arguments");
     if (td.offset != TVM_ONE) return set_error(c, TVM_ERR_UNSUPPORTED, "trace domain offset must be 1");
-    const u64* d_w = stage_small(c, 9, h_weights, 3 * (size_t)n_cols);
+    const u64* d_w = stage_small(c, Scratch::SmallIn, h_weights, 3 * (size_t)n_cols);
     if (!d_w) return set_error(c, TVM_ERR_OUT_OF_MEMORY, "weights staging");
     TVM_TRY(weighted_row_sum(c, fk, d_trace, n, n_cols, d_w, 0, d_poly));
     TVM_HIP_CHECK(c, hipMemsetAsync(d_poly + 3 * n, 0, 3 * n * sizeof(u64), c->stream));
@@ -809,7 +559,7 @@ int32_t tvm_xfe_linear_combination(tvm_ctx* c, const uint64_t* d_vectors, uint32
     if (!c || !d_vectors || !h_weights || !d_out || !n_vectors || n_vectors > 64 || stride < n)
         return set_error(c, TVM_ERR_INVALID_ARGUMENT, "xfe_linear_combination arguments");
     if (!n) return TVM_OK;
-    const u64* d_w = stage_small(c, 9, h_weights, 3 * (size_t)n_vectors);
+    const u64* d_w = stage_small(c, Scratch::SmallIn, h_weights, 3 * (size_t)n_vectors);
     if (!d_w) return set_error(c, TVM_ERR_OUT_OF_MEMORY, "weights staging");
     TVM_LAUNCH(tvm::k_xfe_linear_combination, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, d_vectors, (int)n_vectors, stride, n,
                d_w, d_out);
@@ -821,8 +571,8 @@ int32_t tvm_evaluate_at_points(tvm_ctx* c, const uint64_t* d_coeffs, uint64_t n,
                                uint64_t* h_out) {
     if (!c || (n && !d_coeffs) || !h_points || !h_out || !n_points)
         return set_error(c, TVM_ERR_INVALID_ARGUMENT, "evaluate_at_points arguments");
-    const u64* d_points = stage_small(c, 9, h_points, 3 * (size_t)n_points);
-    u64* d_out = (u64*)scratch(c, 10, (size_t)n_points * 3 * sizeof(u64));
+    const u64* d_points = stage_small(c, Scratch::SmallIn, h_points, 3 * (size_t)n_points);
+    u64* d_out = (u64*)scratch(c, Scratch::SmallOut, (size_t)n_points * 3 * sizeof(u64));
     if (!d_points || !d_out) return set_error(c, TVM_ERR_OUT_OF_MEMORY, "points staging");
     TVM_TRY(poly_eval(c, d_coeffs, n, d_points, (int)n_points, d_out));
     TVM_HIP_CHECK(c, hipMemcpyAsync(h_out, d_out, (size_t)n_points * 3 * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
@@ -834,8 +584,8 @@ int32_t tvm_evaluate_polys_at_points(tvm_ctx* c, const uint64_t* d_coeffs, uint6
                                      const uint64_t* h_points, uint32_t n_points, uint64_t* h_out) {
     if (!c || (n && !d_coeffs) || !h_points || !h_out || !n_points || !n_polys || n_polys > 64 || stride < n)
         return set_error(c, TVM_ERR_INVALID_ARGUMENT, "evaluate_polys_at_points arguments");
-    const u64* d_points = stage_small(c, 9, h_points, 3 * (size_t)n_points);
-    u64* d_out = (u64*)scratch(c, 10, (size_t)n_polys * n_points * 3 * sizeof(u64));
+    const u64* d_points = stage_small(c, Scratch::SmallIn, h_points, 3 * (size_t)n_points);
+    u64* d_out = (u64*)scratch(c, Scratch::SmallOut, (size_t)n_polys * n_points * 3 * sizeof(u64));
     if (!d_points || !d_out) return set_error(c, TVM_ERR_OUT_OF_MEMORY, "points staging");
     // (the partial sums of poly_eval share one scratch slot: the evaluations follow one another on the stream)
     for (uint32_t p = 0; p < n_polys; p++)
@@ -861,7 +611,7 @@ static int quotient_segments_of_coefficients(tvm_ctx* c, const u64* coeffs, u64 
         // More coefficients than points: `ldt` is one rank's share of the LDT domain in a many-GPU split (8 ranks: one coset
         // of the trace domain, half as long as a segment polynomial).  Reduce modulo X^L - offset^L first, which leaves the
         // values on the coset unchanged (arithmetic_domain.rs:153-167); d_polys keeps the polynomials themselves.
-        u64* folded = (u64*)scratch(c, 25, (size_t)15 * L * sizeof(u64));
+        u64* folded = (u64*)scratch(c, Scratch::SegmentFolded, (size_t)15 * L * sizeof(u64));
         if (!folded) return set_error(c, TVM_ERR_OUT_OF_MEMORY, "segment folding scratch");
         for (int k = 0; k < 5; k++)
             TVM_LAUNCH(k_fold_chunks, dim3((unsigned)((3 * L + 255) / 256)), dim3(256), 0, c->stream, d_polys + (u64)k * poly_len * 3,
@@ -890,7 +640,7 @@ static int quotient_segments_of_coefficients(tvm_ctx* c, const u64* coeffs, u64 
         // kernels write it coset-major and row-block-major directly (context.h), at a quarter of the cost per column of X
         // generic coset transforms plus a transposition (5.0 -> 2.4 ms at 2^20 rows).  (The successor blocks stay unfilled:
         // nothing reads the "next" row of a segment.)
-        u64* values = (u64*)scratch(c, 12, (size_t)15 * M * sizeof(u64));
+        u64* values = (u64*)scratch(c, Scratch::SegmentValues, (size_t)15 * M * sizeof(u64));
         if (!values) rc = set_error(c, TVM_ERR_OUT_OF_MEMORY, "segment values scratch");
         const u64 w_m = bfe_pow(ldt.generator, X);
         if (rc == TVM_OK) rc = ntt_columns(c, polys_in, in_len, 3, 3 * in_len, values, 3, 3 * M, 1, 0, 15, M, w_m, TVM_ONE, TVM_ONE, TVM_ONE);
@@ -901,7 +651,7 @@ static int quotient_segments_of_coefficients(tvm_ctx* c, const u64* coeffs, u64 
         if (rc == TVM_OK) rc = lde_table(c, 3, values, M, 5, nullptr, 0, w_m, ldt.offset, ldt.generator, L, t->data, 0);
     } else {
         // evaluate the 5 polynomials (15 base-field columns) into planar codewords, then lay them out as a table
-        u64* planar = (u64*)scratch(c, 12, (size_t)15 * L * sizeof(u64));
+        u64* planar = (u64*)scratch(c, Scratch::SegmentValues, (size_t)15 * L * sizeof(u64));
         if (!planar) rc = set_error(c, TVM_ERR_OUT_OF_MEMORY, "segment codewords scratch");
         for (u64 k = 0; k < X && rc == TVM_OK; k++) {
             const u64 off = bfe_mul(ldt.offset, bfe_pow(ldt.generator, k));
@@ -928,8 +678,8 @@ int32_t tvm_quotient_segments(tvm_ctx* c, const uint64_t* d_cw, tvm_domain qd, t
         poly_len < qd.length / 4 || poly_len < n_rand || ldt.length < 2)
         return set_error(c, TVM_ERR_INVALID_ARGUMENT, "quotient_segments arguments");
     const u64 Q = qd.length;
-    u64* coeffs = (u64*)scratch(c, 11, Q * 3 * sizeof(u64));
-    const u64* d_rnd = stage_small(c, 9, h_rnd, 3 * (size_t)n_rand);
+    u64* coeffs = (u64*)scratch(c, Scratch::QuotientCoefficients, Q * 3 * sizeof(u64));
+    const u64* d_rnd = stage_small(c, Scratch::SmallIn, h_rnd, 3 * (size_t)n_rand);
     if (!coeffs || !d_rnd) return set_error(c, TVM_ERR_OUT_OF_MEMORY, "segments scratch");
     TVM_TRY(tvm_interpolate(c, 3, d_cw, qd, coeffs));
     return quotient_segments_of_coefficients(c, coeffs, Q, ldt, d_rnd, n_rand, zeta, out_table, d_polys, poly_len);
@@ -943,7 +693,7 @@ int32_t tvm_quotient_segments_from_coefficients(tvm_ctx* c, const uint64_t* d_co
     if (!d_coeffs || !d_polys || (n_rand && !h_rnd) || !valid_domain(ldt) || !n_coeffs || poly_len < (n_coeffs + 3) / 4 ||
         poly_len < n_rand || ldt.length < 2)
         return set_error(c, TVM_ERR_INVALID_ARGUMENT, "quotient_segments_from_coefficients arguments");
-    const u64* d_rnd = stage_small(c, 9, h_rnd, 3 * (size_t)n_rand);
+    const u64* d_rnd = stage_small(c, Scratch::SmallIn, h_rnd, 3 * (size_t)n_rand);
     if (!d_rnd) return set_error(c, TVM_ERR_OUT_OF_MEMORY, "segments scratch");
     return quotient_segments_of_coefficients(c, d_coeffs, n_coeffs, ldt, d_rnd, n_rand, zeta, out_table, d_polys, poly_len);
 }
@@ -951,7 +701,7 @@ int32_t tvm_quotient_segments_from_coefficients(tvm_ctx* c, const uint64_t* d_co
 int32_t tvm_table_linear_combination(tvm_ctx* c, const tvm_table* t, uint64_t ldt_length, const uint64_t* h_w, uint64_t* d_out) {
     if (!c || !t || !h_w || !d_out || !is_pow2(ldt_length) || ldt_length > t->rows)
         return set_error(c, TVM_ERR_INVALID_ARGUMENT, "table_linear_combination arguments");
-    const u64* d_w = stage_small(c, 9, h_w, 3 * (size_t)t->n_cols);
+    const u64* d_w = stage_small(c, Scratch::SmallIn, h_w, 3 * (size_t)t->n_cols);
     if (!d_w) return set_error(c, TVM_ERR_OUT_OF_MEMORY, "weights staging");
     return table_lincomb(c, t->data, t->layout, t->fk, t->n_cols, t->rows / ldt_length, d_w, d_out);
 }
@@ -972,7 +722,7 @@ int32_t tvm_fri_commit_phase(tvm_ctx* c, const uint64_t* d_cw, tvm_domain dom, u
         if (!d_nodes[r] || (r < n_rounds && !d_codewords[r])) return set_error(c, TVM_ERR_INVALID_ARGUMENT, "fri_commit_phase: null buffer");
     // device words: the sponge (16), the roots ((n_rounds + 1) * 5), the challenges (n_rounds * 3)
     const size_t n_words = 16 + (size_t)(n_rounds + 1) * 5 + (size_t)n_rounds * 3;
-    u64* d = (u64*)scratch(c, 24, n_words * sizeof(u64));
+    u64* d = (u64*)scratch(c, Scratch::FriTranscript, n_words * sizeof(u64));
     if (!d) return set_error(c, TVM_ERR_OUT_OF_MEMORY, "fri_commit_phase scratch");
     u64 *d_state = d, *d_roots = d + 16, *d_ch = d_roots + (size_t)(n_rounds + 1) * 5;
     TVM_TRY(tvm::h2d_small(c, d_state, h_state, 16 * sizeof(u64)));   // (h_state may be a caller temporary)
@@ -1013,7 +763,7 @@ int32_t tvm_fill_derived_aux_columns(tvm_ctx* c, const uint64_t* d_main_trace, u
                                      const uint64_t* h_challenges) {
     if (!c || !d_main_trace || !d_aux_trace || !h_challenges || n_rows < 2)
         return set_error(c, TVM_ERR_INVALID_ARGUMENT, "tvm_fill_derived_aux_columns arguments");
-    u64* staged = (u64*)scratch(c, 20, (size_t)3 * TVM_NUM_CHALLENGES * sizeof(u64));
+    u64* staged = (u64*)scratch(c, Scratch::FillChallenges, (size_t)3 * TVM_NUM_CHALLENGES * sizeof(u64));
     if (!staged) return set_error(c, TVM_ERR_OUT_OF_MEMORY, "challenge staging");
     TVM_TRY(tvm::h2d_small(c, staged, h_challenges, 3 * TVM_NUM_CHALLENGES * sizeof(u64)));   // (h_challenges may be a caller temporary)
     return fill_degree_lowering(c, 1, const_cast<u64*>(d_main_trace), d_aux_trace, staged, n_rows);
@@ -1039,7 +789,7 @@ int32_t tvm_extend_aux_table(tvm_ctx* c, const uint64_t* d_main_trace, uint64_t*
                              const uint64_t* h_challenges) {
     if (!c || !d_main_trace || !d_aux_trace || !h_challenges || n_rows < 2)
         return set_error(c, TVM_ERR_INVALID_ARGUMENT, "tvm_extend_aux_table arguments");
-    u64* staged = (u64*)scratch(c, 21, (size_t)3 * TVM_NUM_CHALLENGES * sizeof(u64));
+    u64* staged = (u64*)scratch(c, Scratch::ExtendChallenges, (size_t)3 * TVM_NUM_CHALLENGES * sizeof(u64));
     if (!staged) return set_error(c, TVM_ERR_OUT_OF_MEMORY, "challenge staging");
     TVM_TRY(tvm::h2d_small(c, staged, h_challenges, 3 * TVM_NUM_CHALLENGES * sizeof(u64)));   // (h_challenges may be a caller temporary)
     return extend_aux_table(c, d_main_trace, d_aux_trace, staged, n_rows);
@@ -1170,7 +920,7 @@ static int quotient_arguments(tvm_ctx* c, const tvm_table* mt, const tvm_table* 
     return TVM_OK;
 }
 static int stage_quotient_inputs(tvm_ctx* c, const uint64_t* h_challenges, const uint64_t* h_weights, const u64** d_ch, const u64** d_w) {
-    u64* staged = (u64*)scratch(c, 13, (size_t)3 * (TVM_NUM_CHALLENGES + TVM_NUM_QUOTIENT_WEIGHTS) * sizeof(u64));
+    u64* staged = (u64*)scratch(c, Scratch::QuotientInputs, (size_t)3 * (TVM_NUM_CHALLENGES + TVM_NUM_QUOTIENT_WEIGHTS) * sizeof(u64));
     if (!staged) return set_error(c, TVM_ERR_OUT_OF_MEMORY, "challenge staging");
     TVM_TRY(tvm::h2d_small(c, staged, h_challenges, 3 * TVM_NUM_CHALLENGES * sizeof(u64)));
     TVM_TRY(tvm::h2d_small(c, staged + 3 * TVM_NUM_CHALLENGES, h_weights, 3 * TVM_NUM_QUOTIENT_WEIGHTS * sizeof(u64)));
@@ -1357,7 +1107,7 @@ int32_t tvm_air_class_values(tvm_ctx* c, const tvm_table* mt, const tvm_table* a
         !at->has_successor_blocks || mt->layout.X != table_dom.length / N || at->layout.X != mt->layout.X || mt->layout.pitch != at->layout.pitch ||
         mt->layout.pitch % TVM_RB)
         return set_error(c, TVM_ERR_INVALID_ARGUMENT, "air_class_values: tables made by tvm_lde_table over table_domain, one coset of them");
-    u64* staged = (u64*)scratch(c, 13, (size_t)3 * (TVM_NUM_CHALLENGES + TVM_NUM_QUOTIENT_WEIGHTS) * sizeof(u64));
+    u64* staged = (u64*)scratch(c, Scratch::QuotientInputs, (size_t)3 * (TVM_NUM_CHALLENGES + TVM_NUM_QUOTIENT_WEIGHTS) * sizeof(u64));
     if (!staged) return set_error(c, TVM_ERR_OUT_OF_MEMORY, "challenge staging");
     TVM_TRY(tvm::h2d_small(c, staged, h_challenges, 3 * TVM_NUM_CHALLENGES * sizeof(u64)));
     TVM_TRY(tvm::h2d_small(c, staged + 3 * TVM_NUM_CHALLENGES, h_weights, 3 * TVM_NUM_QUOTIENT_WEIGHTS * sizeof(u64)));
@@ -1426,8 +1176,8 @@ int32_t tvm_stir_next_polynomial(tvm_ctx* c, const uint64_t* d_folded_poly, uint
         !valid_domain(work_domain) || n_coeffs > work_domain.length)
         return set_error(c, TVM_ERR_INVALID_ARGUMENT, "stir_next_polynomial arguments");
     const u64 M = work_domain.length;
-    u64* vals = (u64*)scratch(c, 15, (size_t)M * 3 * sizeof(u64));
-    u64* staged = (u64*)scratch(c, 16, (size_t)(k ? k : 1) * 6 * sizeof(u64));
+    u64* vals = (u64*)scratch(c, Scratch::StirValues, (size_t)M * 3 * sizeof(u64));
+    u64* staged = (u64*)scratch(c, Scratch::StirQuotientSet, (size_t)(k ? k : 1) * 6 * sizeof(u64));
     if (!vals || !staged) return set_error(c, TVM_ERR_OUT_OF_MEMORY, "stir scratch");
     if (k) {
         TVM_TRY(tvm::h2d_small(c, staged, h_quotient_set, (size_t)k * 3 * sizeof(u64)));
@@ -1439,7 +1189,7 @@ int32_t tvm_stir_next_polynomial(tvm_ctx* c, const uint64_t* d_folded_poly, uint
     // its 1.2 ms quotient kernel in the Horner loop over 204 coefficients)
     u64* ans_values = nullptr;
     if (k >= 32 && k <= M) {
-        ans_values = (u64*)scratch(c, 17, (size_t)M * 3 * sizeof(u64));
+        ans_values = (u64*)scratch(c, Scratch::StirAnswerValues, (size_t)M * 3 * sizeof(u64));
         if (!ans_values) return set_error(c, TVM_ERR_OUT_OF_MEMORY, "stir scratch");
         TVM_TRY(tvm_evaluate(c, 3, staged + 3 * (size_t)k, k, work_domain, ans_values));
     }
@@ -1455,7 +1205,7 @@ int32_t tvm_xfe_interpolate(tvm_ctx* c, const uint64_t* h_points, const uint64_t
     if (!c || (k && (!h_points || !h_values || !h_out))) return set_error(c, TVM_ERR_INVALID_ARGUMENT, "xfe_interpolate arguments");
     if (!k) return TVM_OK;
     if (k > 256) return tvm_host_xfe_interpolate(h_points, h_values, k, h_out);
-    u64* d = (u64*)scratch(c, 27, (size_t)(9 * k + 2) * sizeof(u64));
+    u64* d = (u64*)scratch(c, Scratch::InterpolationStaging, (size_t)(9 * k + 2) * sizeof(u64));
     if (!d) return set_error(c, TVM_ERR_OUT_OF_MEMORY, "interpolation staging");
     int* d_status = (int*)(d + 9 * k);
     TVM_HIP_CHECK(c, hipMemcpyAsync(d, h_points, 3 * (size_t)k * sizeof(u64), hipMemcpyHostToDevice, c->stream));
@@ -1554,8 +1304,8 @@ int32_t tvm_gather_elements(tvm_ctx* c, const uint64_t* d_src, uint32_t elem_wor
                             uint64_t* h_out) {
     if (!c || !d_src || !elem_words || (n && (!h_idx || !h_out))) return set_error(c, TVM_ERR_INVALID_ARGUMENT, "gather arguments");
     if (!n) return TVM_OK;
-    u64* d_idx = (u64*)scratch(c, 4, n * sizeof(u64));
-    u64* d_out = (u64*)scratch(c, 5, n * elem_words * sizeof(u64));
+    u64* d_idx = (u64*)scratch(c, Scratch::GatherIndices, n * sizeof(u64));
+    u64* d_out = (u64*)scratch(c, Scratch::GatherOut, n * elem_words * sizeof(u64));
     if (!d_idx || !d_out) return set_error(c, TVM_ERR_OUT_OF_MEMORY, "gather scratch");
     TVM_TRY(tvm::h2d_small(c, d_idx, h_idx, n * sizeof(u64)));
     const u64 total = n * elem_words;
@@ -1584,8 +1334,8 @@ int32_t tvm_gather_elements_batch(tvm_ctx* c, uint32_t n_jobs, const uint64_t* c
         std::memcpy(idx.data() + at, h_idx[j], n[j] * sizeof(u64));
         at += n[j];
     }
-    u64* d_idx = (u64*)scratch(c, 4, n_idx * sizeof(u64));
-    u64* d_out = (u64*)scratch(c, 5, n_words * sizeof(u64));
+    u64* d_idx = (u64*)scratch(c, Scratch::GatherIndices, n_idx * sizeof(u64));
+    u64* d_out = (u64*)scratch(c, Scratch::GatherOut, n_words * sizeof(u64));
     if (!d_idx || !d_out) return set_error(c, TVM_ERR_OUT_OF_MEMORY, "gather scratch");
     TVM_TRY(tvm::h2d_small(c, d_idx, idx.data(), n_idx * sizeof(u64)));
     u64 i0 = 0, w0 = 0;

@@ -1,4 +1,4 @@
-// context.h -- device context shared by all entry points of libtriton_hip.so.
+// context.h -- device context shared by all entry points of libtriton_hip.so (implemented in context.hip).
 //
 // One context per host thread that proves (the reference's prove() may run concurrently on several
 // threads, /root/reference/triton-vm/src/lib.rs:522-532): a context owns one HIP stream, a cache of
@@ -8,7 +8,6 @@
 #include <map>
 #include <string>
 #include <tuple>
-#include <vector>
 
 #include "field.h"
 #include "triton_hip.h"  // status codes and the public C ABI (include/)
@@ -90,16 +89,85 @@ inline TabView tab_view(const TabLayout& l, u64 stride) {
     return v;
 }
 
+namespace tvm {
+// The scratch slots of a context (scratch(), stage_small()): one device block each, grown on demand, kept until tvm_ctx_destroy.
+//
+// THE RULE.  A slot belongs to the function that asks for it until that function returns -- the kernels it has launched read and
+// write the block in stream order, and asking for a slot AGAIN with a larger size frees the old block.  So a function may hold a
+// slot across a call only if nothing that call can reach asks for the same slot.  The enumerators are grouped in three layers, and
+// calls go downwards only; a function asks for slots of its own layer alone:
+//   * entry-point slots: asked for by an extern "C" entry point (or a static helper that only it calls), which may hold them across
+//     any call into the layers below.  Entry points do not call entry points that take entry-point slots: the ones that are called
+//     from others (tvm_evaluate, tvm_interpolate) take helper and unit slots only.  Entry points that share a slot
+//     (GatherIndices / GatherOut, SmallIn / SmallOut, QuotientInputs) never call one another.
+//   * helper slots: tvm_evaluate and quotient_segments_of_coefficients (capi.hip), held across calls into the units.
+//   * unit slots: asked for inside a kernel unit (ntt.hip, air.hip, poly.hip, pad.hip) by a function that calls no other function
+//     that takes a slot -- the bottom; every caller above may rely on their being distinct from its own.
+// The cases that decide it:
+//   * tvm_all_quotients_combined / _coefficients and tvm_air_class_values hold QuotientInputs while air.hip takes ZerofierInverses
+//     and AirAccumulators, and (valid-trace mode) while tvm_evaluate / tvm_interpolate take FoldedCoefficients and NttTemp;
+//   * tvm_quotient_segments holds QuotientCoefficients and SmallIn across quotient_segments_of_coefficients, which holds SegmentFolded
+//     and SegmentValues across ntt_columns (NttTemp); lde_table takes its intermediates from the pool;
+//   * tvm_stir_next_polynomial holds StirValues, StirQuotientSet and StirAnswerValues across tvm_evaluate and tvm_interpolate;
+//   * tvm_check_constraints holds its first six across air_on_rows (AirAccumulators; the selectors take the place of the zerofier
+//     inverses), and takes the last two after the screen's results are on the host.
+// A new unit takes NEW enumerators in the layer it calls from; it shares an existing one only where this comment says why it may.
+enum class Scratch : int {
+    // ---- unit slots
+    NttTemp,                // ntt_columns: the columns between its two passes
+    ZerofierInverses,       // air.hip: four factors per row of the quotient domain
+    AirAccumulators,        // air.hip: the quotient values in work order, one set per lane
+    OodWeights,             // out_of_domain_rows: the barycentric weights, per point and row
+    OodSums,                // out_of_domain_rows: numerators and denominator per point
+    ReductionPartials,      // out_of_domain_rows, poly_eval: per-workgroup partial sums (the evaluations follow one another on the stream)
+    PadPivot,               // pad_main_table: one word
+    // ---- helper slots
+    FoldedCoefficients,     // tvm_evaluate: more coefficients than points, reduced modulo X^L - offset^L
+    SegmentFolded,          // quotient_segments_of_coefficients: the same reduction of the five segment polynomials
+    SegmentValues,          // ... and their values, on the M-th roots of unity or (short domains) as planar codewords
+    // ---- entry-point slots
+    GatherIndices,          // tvm_table_reveal_rows, tvm_gather_elements(_batch): the indices ...
+    GatherOut,              // ... and what they select, on its way to the host
+    SmallIn,                // a small host array in (points, weights, randomizers): every entry point that stages one
+    SmallOut,               // ... and a small result on its way out (rows, values at the points)
+    QuotientCoefficients,   // tvm_quotient_segments: the interpolated quotient
+    QuotientInputs,         // challenges and quotient weights: both quotient entry points, tvm_air_class_values
+    StirValues,             // tvm_stir_next_polynomial: the folded polynomial on the work domain
+    StirQuotientSet,        // ... the quotient set and the answer polynomial
+    StirAnswerValues,       // ... the answer polynomial on the work domain
+    FillChallenges,         // tvm_fill_derived_aux_columns
+    ExtendChallenges,       // tvm_extend_aux_table
+    FriTranscript,          // tvm_fri_commit_phase: sponge, roots, challenges
+    InterpolationStaging,   // tvm_xfe_interpolate: points, values, coefficients, status
+    AirCheckInputs,         // tvm_check_constraints: challenges and the screen's weights
+    AirCheckSelectors,      // ... four factors per row of a chunk
+    AirCheckValues,         // ... the screen's value per row
+    AirCheckOffsets,        // ... per-group offsets and the running total
+    AirCheckCounts,         // ... per-group counts
+    AirCheckListed,         // ... the failing rows
+    AirCheckPairIndices,    // ... pinpointing: rows r, r + 1 of a batch of listed rows
+    AirCheckPairs,          // ... and their words
+    Count
+};
+// The kinds of constant table a context caches (cached_table); what the three key words mean is the kind's own business:
+//   Powers             (base, count, scale): t[i] = scale * base^i                                             pow_table
+//   CosetFactors       (offset, generator, X << 56 | n1 << 28 | n2): lo / hi of the X cosets                   ntt.hip: coset_tables
+//   Pass2Twiddles      (trace generator, n1, n2): f of k_lde_pass2_fused                                       ntt.hip: pass2_fused_tables
+//   Pass2CosetFactors  (offset, generator, X << 56 | n1 << 28 | n2): hi_pos and u of k_lde_pass2_fused
+//   Pass3Halves        (root of the n1-point axis, 2048, 0): the twiddles of k_lde_pass3_halves                ntt.hip: lde_table
+enum class TableKind { Powers, CosetFactors, Pass2Twiddles, Pass2CosetFactors, Pass3Halves };
+}  // namespace tvm
+
 struct tvm_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
     bool owns_stream = false;
-    std::map<std::tuple<u64, u64, u64>, u64*> tables;  // (base, count, scale) -> device table
-    std::vector<void*> scratch;                         // named scratch slots
-    std::vector<size_t> scratch_bytes;
+    std::map<std::tuple<tvm::TableKind, u64, u64, u64>, u64*> tables;   // cached_table: (kind, three words) -> device table
+    void* scratch[(int)tvm::Scratch::Count] = {};       // the scratch slots and their capacities
+    size_t scratch_bytes[(int)tvm::Scratch::Count] = {};
     // Caching device allocator: every device block handed out by the library (tvm_malloc, table handles)
     // comes from here and returns here; a 2^20-row proof allocates ~45 GiB of tables per prove(), and
-    // hipMalloc/hipFree of that size cost hundreds of milliseconds each.  Blocks are reused in stream
+    // driver allocations and frees of that size cost hundreds of milliseconds each.  Blocks are reused in stream
     // order (one stream per context), so handing a freed block to the next request needs no host sync.
     std::multimap<size_t, void*> pool_free;             // capacity -> block
     std::map<void*, size_t> pool_live;                  // block -> capacity
@@ -120,7 +188,7 @@ struct tvm_ctx {
     char* pin = nullptr;
     size_t pin_bytes = 0, pin_head = 0;
     bool pin_unavailable = false;   // hipHostMalloc refused once: the plain path (copy, then wait) from then on
-    // the fork lanes (air.hip: all_quotients_combined): launches that are independent of one another and too small to fill the
+    // the fork lanes (fork_lanes; air.hip: air_run): launches that are independent of one another and too small to fill the
     // chip each -- the parts of the AIR on a short quotient domain -- go out on these streams beside the context's own and meet
     // it again before the next dependent launch.  Created on first use.
     hipStream_t fork[3] = {};
@@ -140,15 +208,27 @@ struct LdeSplit {
     u64* coeffs;
     int first_vcol, n_vcols;
 };
+// The driver allocates on the calling thread's CURRENT device, and streams belong to the device that is current when they are created;
+// another context (or the application) may have changed it since tvm_ctx_create.  Every path that allocates or creates a stream
+// selects the context's device first -- and leaves it selected (only tvm_ctx_memory_info puts the caller's device back).
+bool bind_device(tvm_ctx* c);
+// The cached table (kind, a, b, d) of `words` words, for the life of the context.  On a miss the block is allocated on the context's
+// device and registered, and *is_new tells the caller to launch its fill on c->stream.  nullptr: the device refused.
+u64* cached_table(tvm_ctx* c, TableKind kind, u64 a, u64 b, u64 d, u64 words, bool* is_new);
+// takes back (and frees) a table registered by a cached_table whose fill will not be launched
+void drop_cached_table(tvm_ctx* c, TableKind kind, u64 a, u64 b, u64 d);
 // t[i] = scale * base^i, i < count (Montgomery words); cached for the life of the context
 const u64* pow_table(tvm_ctx* c, u64 base, u64 count, u64 scale = TVM_ONE);
-// scratch slot `slot` of at least `bytes` bytes (grown on demand, contents undefined)
-void* scratch(tvm_ctx* c, int slot, size_t bytes);
+// scratch slot `slot` of at least `bytes` bytes (grown on demand, contents undefined); see the rule above Scratch
+void* scratch(tvm_ctx* c, Scratch slot, size_t bytes);
+// a small host array (points, weights) staged into a scratch slot through h2d_small; nullptr on failure
+const u64* stage_small(tvm_ctx* c, Scratch slot, const u64* h, size_t words);
 int set_error(tvm_ctx* c, int code, const char* what);
 // pool: nullptr on device out-of-memory (after the cache has been given back to the driver and the request retried)
 void* pool_alloc(tvm_ctx* c, size_t bytes);
 void pool_release(tvm_ctx* c, void* p);   // back to the cache (stream-ordered reuse)
 void pool_trim(tvm_ctx* c);               // cached blocks back to the driver (synchronises the stream)
+// what a pool_alloc could still obtain: the device's free memory plus this context's cached blocks, capped by the context's limit
 size_t pool_available(tvm_ctx* c, size_t* device_total);
 // Host array -> device, stream-ordered, WITHOUT draining the stream: the bytes are copied into the context's pinned staging ring and
 // go from there (the caller's array may be a temporary: it is free on return).  The ring wraps after a stream synchronisation -- once
@@ -156,7 +236,7 @@ size_t pool_available(tvm_ctx* c, size_t* device_total);
 // was hipMemcpyAsync + hipStreamSynchronize: some twenty drained streams per proof, a fifth of a proof of a 2^10-row trace.
 int h2d_small(tvm_ctx* c, void* d, const void* h, size_t bytes);
 // the context's fork lanes (three more streams and their events), created on first use; false if the driver refuses
-bool fork_lanes(tvm_ctx* c);   // device free + own cache, capped by the context's limit
+bool fork_lanes(tvm_ctx* c);
 // a pool block that goes back to the cache on every exit path of the function that holds it
 struct PoolBlock {
     tvm_ctx* c;

@@ -44,11 +44,6 @@ struct Pow2 {  // t^e = lo[e & mask] * hi[e >> shift]
 };
 TVM_D u64 pow2_get(const Pow2& t, u64 e) { return bfe_mul(t.lo[e & ((1ull << t.shift) - 1)], t.hi[e >> t.shift]); }
 
-__global__ void k_pow_table(u64 base, u64 count, u64 scale, u64* out) {
-    u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < count) out[i] = bfe_mul(scale, bfe_pow(base, i));
-}
-
 // In-LDS transform of a tile: element (a, b) at s[a*SA + b*SB], a < 2^log_n the transform axis,
 // b < 2^batch_log independent transforms.  tw[e] = w^e, e < n (all n powers: the twiddle steps of lds_ntt_group use the
 // upper half too), w the n-th root to use.
@@ -1134,148 +1129,7 @@ __global__ void k_pass2_fused_tables(const u64* __restrict__ lo, const u64* __re
 
 // ------------------------------------------------------------------------------------------------
 // host side
-// hipMalloc allocates on the calling thread's CURRENT device, which another context (or the application) may have
-// changed since tvm_ctx_create: every allocating path re-selects the context's device first.
-static bool bind_device(tvm_ctx* c) {
-    int cur = -1;
-    if (hipGetDevice(&cur) == hipSuccess && cur == c->device) return true;
-    return hipSetDevice(c->device) == hipSuccess;
-}
-
-const u64* pow_table(tvm_ctx* c, u64 base, u64 count, u64 scale) {
-    auto key = std::make_tuple(base, count, scale);
-    auto it = c->tables.find(key);
-    if (it != c->tables.end()) return it->second;
-    u64* d = nullptr;
-    if (!bind_device(c)) return nullptr;
-    if (hipMalloc((void**)&d, (count ? count : 1) * sizeof(u64)) != hipSuccess) return nullptr;
-    const int bs = 256;
-    TVM_LAUNCH(k_pow_table, dim3((unsigned)((count + bs - 1) / bs)), dim3(bs), 0, c->stream, base, count, scale, d);
-    c->tables[key] = d;
-    return d;
-}
-
-void* scratch(tvm_ctx* c, int slot, size_t bytes) {
-    if ((size_t)slot >= c->scratch.size()) {
-        c->scratch.resize(slot + 1, nullptr);
-        c->scratch_bytes.resize(slot + 1, 0);
-    }
-    if (c->scratch_bytes[slot] < bytes) {
-        if (c->scratch[slot]) {
-            (void)hipStreamSynchronize(c->stream);
-            (void)hipFree(c->scratch[slot]);
-            c->scratch[slot] = nullptr;
-            c->scratch_bytes[slot] = 0;
-        }
-        void* p = nullptr;
-        if (!bind_device(c) || hipMalloc(&p, bytes) != hipSuccess) return nullptr;
-        c->scratch[slot] = p;
-        c->scratch_bytes[slot] = bytes;
-    }
-    return c->scratch[slot];
-}
-
-static size_t pool_round(size_t bytes) {
-    const size_t g = bytes < (1u << 20) ? 256 : (2u << 20);
-    return (bytes + g - 1) / g * g;
-}
-void* pool_alloc(tvm_ctx* c, size_t bytes) {
-    const size_t want = pool_round(bytes ? bytes : 1);
-    auto it = c->pool_free.lower_bound(want);
-    if (it != c->pool_free.end() && it->first <= want + want / 4) {  // at most 25 % slack
-        void* p = it->second;
-        c->pool_live[p] = it->first;
-        c->pool_free.erase(it);
-        return p;
-    }
-    void* p = nullptr;
-    if (!bind_device(c)) return nullptr;
-    if (c->pool_limit && c->pool_bytes + want > c->pool_limit) {
-        pool_trim(c);  // cached blocks count against the limit: give them back first
-        if (c->pool_bytes + want > c->pool_limit) return nullptr;
-    }
-    if (hipMalloc(&p, want) != hipSuccess) {
-        (void)hipGetLastError();
-        pool_trim(c);
-        if (hipMalloc(&p, want) != hipSuccess) {
-            (void)hipGetLastError();
-            return nullptr;
-        }
-    }
-    c->pool_live[p] = want;
-    c->pool_bytes += want;
-    return p;
-}
-void pool_release(tvm_ctx* c, void* p) {
-    if (!p) return;
-    auto it = c->pool_live.find(p);
-    if (it == c->pool_live.end()) {  // not ours (should not happen): hand it to the driver
-        (void)hipStreamSynchronize(c->stream);
-        (void)hipFree(p);
-        return;
-    }
-    c->pool_free.emplace(it->second, p);
-    c->pool_live.erase(it);
-}
-void pool_trim(tvm_ctx* c) {
-    if (c->pool_free.empty()) return;
-    (void)hipStreamSynchronize(c->stream);
-    for (auto& kv : c->pool_free) {
-        (void)hipFree(kv.second);
-        c->pool_bytes -= kv.first;
-    }
-    c->pool_free.clear();
-}
-
-// what a pool_alloc could still obtain: the device's free memory plus this context's cached blocks, capped by the limit
-int h2d_small(tvm_ctx* c, void* d, const void* h, size_t bytes) {
-    if (!bytes) return TVM_OK;
-    constexpr size_t RING = (size_t)4 << 20;
-    if (!c->pin && !c->pin_unavailable) {
-        void* p = nullptr;
-        if (bind_device(c) && hipHostMalloc(&p, RING, 0) == hipSuccess) {
-            c->pin = (char*)p;
-            c->pin_bytes = RING;
-        } else {
-            (void)hipGetLastError();
-            c->pin_unavailable = true;
-        }
-    }
-    if (!c->pin || bytes > c->pin_bytes / 4) {
-        TVM_HIP_CHECK(c, hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, c->stream));
-        TVM_HIP_CHECK(c, hipStreamSynchronize(c->stream));
-        return TVM_OK;
-    }
-    const size_t need = (bytes + 63) & ~(size_t)63;
-    if (c->pin_head + need > c->pin_bytes) {   // wrap: every copy out of the ring so far has been issued on this stream
-        TVM_HIP_CHECK(c, hipStreamSynchronize(c->stream));
-        c->pin_head = 0;
-    }
-    char* slot = c->pin + c->pin_head;
-    c->pin_head += need;
-    std::memcpy(slot, h, bytes);
-    TVM_HIP_CHECK(c, hipMemcpyAsync(d, slot, bytes, hipMemcpyHostToDevice, c->stream));
-    return TVM_OK;
-}
-size_t pool_available(tvm_ctx* c, size_t* device_total) {
-    size_t free_b = 0, total_b = 0;
-    if (!bind_device(c) || hipMemGetInfo(&free_b, &total_b) != hipSuccess) return 0;
-    size_t cached = 0;
-    for (const auto& kv : c->pool_free) cached += kv.first;
-    size_t avail = free_b + cached;
-    if (c->pool_limit) {
-        const size_t live = c->pool_bytes - cached;
-        avail = live >= c->pool_limit ? 0 : (avail < c->pool_limit - live ? avail : c->pool_limit - live);
-    }
-    if (device_total) *device_total = total_b;
-    return avail;
-}
-
-int set_error(tvm_ctx* c, int code, const char* what) {
-    if (c) c->last_error = what;
-    return code;
-}
-
+// (the context's services -- pow_table, cached_table, scratch, the pool -- are context.hip's)
 static int threads_for_tile(int tile) {
     int t = tile / 16;
     t = (t + 63) / 64 * 64;
@@ -1331,19 +1185,13 @@ __global__ void k_coset_tables(u64 offset, u64 gen, u64 X, u64 n1, u64 n2, u64 s
     else hi[k * n2 + (i - n1)] = bfe_pow(bfe_pow(gamma, n1), i - n1);
 }
 static int coset_tables(tvm_ctx* c, u64 offset, u64 gen, u64 X, u64 n1, u64 n2, u64 scale, const u64** lo, const u64** hi) {
-    auto key = std::make_tuple(offset ^ 0xC05E7C05E7ull, gen, (X << 56) | (n1 << 28) | n2);
-    auto it = c->tables.find(key);
-    u64* d = nullptr;
-    if (it != c->tables.end()) {
-        d = it->second;
-    } else {
-        if (hipMalloc((void**)&d, X * (n1 + n2) * sizeof(u64)) != hipSuccess)
-            return set_error(c, TVM_ERR_OUT_OF_MEMORY, "coset tables");
-        const u64 total = X * (n1 + n2);
+    const u64 total = X * (n1 + n2);
+    bool is_new = false;
+    u64* d = cached_table(c, TableKind::CosetFactors, offset, gen, (X << 56) | (n1 << 28) | n2, total, &is_new);
+    if (!d) return set_error(c, TVM_ERR_OUT_OF_MEMORY, "coset tables");
+    if (is_new)
         TVM_LAUNCH(k_coset_tables, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, c->stream, offset, gen, X, n1, n2,
                    scale, d, d + X * n1);
-        c->tables[key] = d;
-    }
     *lo = d;
     *hi = d + X * n1;
     return TVM_OK;
@@ -1353,17 +1201,15 @@ static int coset_tables(tvm_ctx* c, u64 offset, u64 gen, u64 X, u64 n1, u64 n2, 
 static int pass2_fused_tables(tvm_ctx* c, u64 trace_gen, u64 offset, u64 gen, u64 X, int log_n1, int log_n2, const u64* lo, const u64* hi,
                               const Pow2& tw_inter, const u64* tw_n2, const u64** hi_pos, const u64** f, const u64** u) {
     const u64 n1 = 1ull << log_n1, n2 = 1ull << log_n2, n = n1 * n2;
-    const auto key_f = std::make_tuple(trace_gen ^ 0xF05EDF05EDull, n1, n2);
-    const auto key_k = std::make_tuple(offset ^ 0xF05EDC05E7ull, gen, (X << 56) | (n1 << 28) | n2);
-    auto it_f = c->tables.find(key_f);
-    auto it_k = c->tables.find(key_k);
-    u64 *d_f = it_f != c->tables.end() ? it_f->second : nullptr, *d_k = it_k != c->tables.end() ? it_k->second : nullptr;
-    const bool new_f = !d_f, new_k = !d_k;
-    if (!bind_device(c)) return set_error(c, TVM_ERR_DEVICE, "bind device");
-    if (new_f && hipMalloc((void**)&d_f, n * sizeof(u64)) != hipSuccess) return set_error(c, TVM_ERR_OUT_OF_MEMORY, "pass-2 twiddle table");
+    const u64 sizes = (X << 56) | (n1 << 28) | n2;
     const u64 r3 = n2 >> 8;   // radix of the last butterfly group
-    if (new_k && hipMalloc((void**)&d_k, X * (n2 + r3 * n1) * sizeof(u64)) != hipSuccess) {
-        if (new_f) (void)hipFree(d_f);
+    if (!bind_device(c)) return set_error(c, TVM_ERR_DEVICE, "bind device");
+    bool new_f = false, new_k = false;
+    u64* d_f = cached_table(c, TableKind::Pass2Twiddles, trace_gen, n1, n2, n, &new_f);
+    if (!d_f) return set_error(c, TVM_ERR_OUT_OF_MEMORY, "pass-2 twiddle table");
+    u64* d_k = cached_table(c, TableKind::Pass2CosetFactors, offset, gen, sizes, X * (n2 + r3 * n1), &new_k);
+    if (!d_k) {
+        if (new_f) drop_cached_table(c, TableKind::Pass2Twiddles, trace_gen, n1, n2);   // (its fill is the launch below)
         return set_error(c, TVM_ERR_OUT_OF_MEMORY, "pass-2 coset tables");
     }
     if (new_f || new_k) {
@@ -1371,8 +1217,6 @@ static int pass2_fused_tables(tvm_ctx* c, u64 trace_gen, u64 offset, u64 gen, u6
         // (entries that exist already are simply written again with the same values when only one of the two is new)
         TVM_LAUNCH(k_pass2_fused_tables, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, c->stream, lo, hi, tw_inter, tw_n2, log_n1,
                    log_n2, X, d_k, new_f ? d_f : (u64*)nullptr, d_k + X * n2);
-        if (new_f) c->tables[key_f] = d_f;
-        if (new_k) c->tables[key_k] = d_k;
     }
     *f = d_f;
     *hi_pos = d_k;
@@ -1435,7 +1279,7 @@ int ntt_columns(tvm_ctx* c, const u64* in, u64 in_len, int in_fk, u64 in_col_str
     Ntt2Args a;
     a.in = in;
     a.out = out;
-    a.tmp = (u64*)scratch(c, 0, (size_t)ncols * n * sizeof(u64));
+    a.tmp = (u64*)scratch(c, Scratch::NttTemp, (size_t)ncols * n * sizeof(u64));
     if (!a.tmp) return set_error(c, TVM_ERR_OUT_OF_MEMORY, "ntt scratch");
     a.log_n1 = sp.log_n1;
     a.log_n2 = sp.log_n2;
@@ -1699,15 +1543,10 @@ int lde_table(tvm_ctx* c, int fk, const u64* trace, u64 n_rows, u64 n_cols, cons
                 const dim3 g3((unsigned)nc, (unsigned)(tiles_w / a.tiles));
                 if (sp.log_n1 == 11 && c->lde_pass2_tiles == 0) {
                     // 2048-point rows as two 1024-point halves through one LDS region per wavefront (k_lde_pass3_halves)
-                    const auto key = std::make_tuple(bfe_pow(w, n2) ^ 0xFB7AB1EFB7ull, (u64)2048, (u64)0);
-                    auto found = c->tables.find(key);
-                    u64* fb = found != c->tables.end() ? found->second : nullptr;
-                    if (!fb) {
-                        if (!bind_device(c) || hipMalloc((void**)&fb, 1024 * sizeof(u64)) != hipSuccess)
-                            return set_error(c, TVM_ERR_OUT_OF_MEMORY, "pass-3 twiddle table");
-                        TVM_LAUNCH(k_pass3_halves_table, dim3(4), dim3(256), 0, c->stream, a.tw_b2, fb);
-                        c->tables[key] = fb;
-                    }
+                    bool is_new = false;
+                    u64* fb = cached_table(c, TableKind::Pass3Halves, bfe_pow(w, n2), 2048, 0, 1024, &is_new);
+                    if (!fb) return set_error(c, TVM_ERR_OUT_OF_MEMORY, "pass-3 twiddle table");
+                    if (is_new) TVM_LAUNCH(k_pass3_halves_table, dim3(4), dim3(256), 0, c->stream, a.tw_b2, fb);
                     a.fb_tw = fb;
                     const size_t lds_h = (size_t)(8 * TVM_ROW_WORDS(1024) + 1024) * sizeof(u64);
                     TVM_LAUNCH((k_lde_pass3_halves<8>), g3, dim3(512), lds_h, c->stream, a);

@@ -474,8 +474,8 @@ __global__ void k_fri_fold(const u64* __restrict__ f, u64 n, u64 offset_inv, u64
 // h_points: n_points XFE; rows_out (device): [n_points][n_cols] XFE
 int out_of_domain_rows(tvm_ctx* c, int fk, const u64* trace, u64 n, u64 n_cols, const u64* rnd, u64 h, u64 trace_gen,
                        const u64* d_points, int n_points, u64* d_rows) {
-    u64* u = (u64*)scratch(c, 6, (size_t)n_points * n * 3 * sizeof(u64));
-    u64* num = (u64*)scratch(c, 7, (size_t)n_points * (n_cols + 1) * 3 * sizeof(u64));
+    u64* u = (u64*)scratch(c, Scratch::OodWeights, (size_t)n_points * n * 3 * sizeof(u64));
+    u64* num = (u64*)scratch(c, Scratch::OodSums, (size_t)n_points * (n_cols + 1) * 3 * sizeof(u64));
     if (!u || !num) return set_error(c, TVM_ERR_OUT_OF_MEMORY, "ood scratch");
     TVM_LAUNCH(k_ood_weights, TVM_GRID(n, 256), dim3(256), 0, c->stream, trace_gen, n, d_points, n_points, u);
     // rows in chunks of 2^15 (128 rows per work-item), columns in groups of G (2 columns: the accumulators' registers and the
@@ -486,7 +486,7 @@ int out_of_domain_rows(tvm_ctx* c, int fk, const u64* trace, u64 n, u64 n_cols, 
     const u64 rows_per_chunk = n < (1ull << chunk_log) ? n : (1ull << chunk_log);
     const u64 n_chunks = (n + rows_per_chunk - 1) / rows_per_chunk;
     const u64 n_sums = (u64)n_points * (n_cols + 1);
-    u64* partial = (u64*)scratch(c, 8, (size_t)n_sums * n_chunks * 3 * sizeof(u64));
+    u64* partial = (u64*)scratch(c, Scratch::ReductionPartials, (size_t)n_sums * n_chunks * 3 * sizeof(u64));
     if (!partial) return set_error(c, TVM_ERR_OUT_OF_MEMORY, "ood scratch");
     const dim3 grid((unsigned)((n_cols + 1 + G - 1) / G), (unsigned)n_chunks);
     for (int p0 = 0; p0 < n_points; p0 += TVM_DOT_P) {
@@ -544,7 +544,7 @@ int poly_eval(tvm_ctx* c, const u64* d_coeffs, u64 n, const u64* d_points, int n
     }
     u64 blocks = (n + TVM_RED_BLOCK * 16 - 1) / (TVM_RED_BLOCK * 16);
     if (blocks > 1024) blocks = 1024;
-    u64* partial = (u64*)scratch(c, 8, (size_t)n_points * blocks * 3 * sizeof(u64));
+    u64* partial = (u64*)scratch(c, Scratch::ReductionPartials, (size_t)n_points * blocks * 3 * sizeof(u64));
     if (!partial) return set_error(c, TVM_ERR_OUT_OF_MEMORY, "poly_eval scratch");
     TVM_LAUNCH(k_poly_eval_partial, dim3((unsigned)blocks, (unsigned)n_points), dim3(TVM_RED_BLOCK), 0, c->stream, d_coeffs,
                n, d_points, partial);
