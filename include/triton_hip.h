@@ -77,8 +77,13 @@ int32_t tvm_ctx_trim(tvm_ctx* ctx);
  * environment. */
 #define TVM_OPTION_LDE_CHUNK_COLUMNS 2
 #define TVM_OPTION_MERKLE_MIN_WORKGROUPS 3
-/* TVM_OPTION_LDE_PASS2_TILES = 1: the middle pass of tvm_lde_table on 2048-point axes (2^21 / 2^22 rows) runs the position-major tile
- * kernel (k_lde_pass2_v3) instead of k_lde_pass2_fused (and the generic kernel on 1024-point axes): the A/B switch of profiles/r05_*. */
+/* TVM_OPTION_LDE_PASS2_TILES = 1: tvm_lde_table runs the kernels that the row kernels replaced (A/B, profiles/r05_* and r06_*; the
+ * tests use it to reach those kernels at small sizes).  A trace of 2^n rows is transformed as n1 x n2 points, n1 = 2^(n/2) rounded
+ * down.  Middle pass (axis n2): never k_lde_pass2_fused -- the tile kernel k_lde_pass2_v3 on 256-, 2048- and 4096-point axes, the
+ * generic kernel on 512- and 1024-point ones.  First and last pass (axis n1): the generic kernels instead of the row kernels on 256-
+ * and 512-point axes (the last pass: the tile kernel k_lde_pass3_v3 at 256 points) and in the first pass at 2048 points; the last pass
+ * at 2048 points runs k_lde_pass3_rows instead of k_lde_pass3_halves.  1024-point axes keep the row kernels of the first and last
+ * pass, and axes of at most 128 or of 4096 points run the same kernels with either value (csrc/lde_plan.h decides all of this). */
 #define TVM_OPTION_LDE_PASS2_TILES 4
 /* TVM_OPTION_AIR_FORK_MAX_WORKGROUPS (default 256; 0 = never): tvm_all_quotients_combined / tvm_air_class_values on a quotient domain of at
  * most this many workgroups of 256 rows launch the parts of the AIR on four streams side by side (the context's and three of its

@@ -31,6 +31,7 @@
 #include <cstring>
 
 #include "context.h"
+#include "lde_plan.h"   // the LDS layouts (TVM_ROW_PAD, TVM_ROW_WORDS, TVM_P2F_*), the split modes, and the host side's choice of kernels
 #include "ntt_shift.h"
 
 namespace tvm {
@@ -56,7 +57,6 @@ TVM_D u64 pow2_get(const Pow2& t, u64 e) { return bfe_mul(t.lo[e & ((1ull << t.s
 // instead of 10 and synchronises 3 times instead of 10.  Lanes of a wavefront are consecutive b first
 // (SB is either 1 or an odd row pitch), then consecutive groups: at most 2-way bank conflicts.
 // Ends with a barrier; the caller must have synchronised the tile before the call.
-#define TVM_ROW_PAD 1
 // CL / CLOGN >= 0: the group's first layer and the transform length are compile-time constants, for the
 // production tile (16 transforms side by side, element (a, b) at s[a + b * (n + TVM_ROW_PAD)]): every LDS address
 // of the group is then the work-item's base plus an immediate offset, and the twiddle indices are shifts by
@@ -184,7 +184,7 @@ TVM_D void lds_ntt_fixed(u64* s, const u64* __restrict__ tw, int tid, int nt) {
 #define TVM_TW_BATCH 0   // twiddle loads in flight per batch in row_ntt_group (0: let the compiler schedule them)
 #endif
 #define TVM_ROW_SKEW(p) ((p) + ((p) >> 4))
-#define TVM_ROW_WORDS(n) ((n) + ((n) >> 4) + 1)   // odd pitch: position p of the 16 rows of a tile falls into 16 different banks
+// (TVM_ROW_WORDS(n), the row pitch: lde_plan.h)
 // LPR: lanes per row -- 64 (the row's own wavefront; tvm_wave_sync between groups), 128 (two wavefronts share a row of 2048 points,
 // `lane` is the lane number within the pair, and the groups are separated by workgroup barriers: every wavefront of the workgroup runs
 // the same sequence), or 32 / 16 (round 6: rows of 512 / 256 points, two / four of them per wavefront, `lane` the number within the
@@ -354,8 +354,6 @@ __global__ void __launch_bounds__(1024) k_ntt2_pass2(Ntt2Args a) {
 // Master-table LDE, passes 2 and 3 (pass 1 is k_ntt2_pass1 with inverse tables).
 #define TVM_LDE_MAX_COSETS 32
 #define TVM_LDE_E 16  // coefficients a thread keeps in VGPRs across the coset loop
-#define TVM_LDE_INVERSE_ONLY 1
-#define TVM_LDE_FORWARD_ONLY 2
 
 struct LdePass2Args {
     const u64* y;        // [cols][N1 positions p][N2]
@@ -922,11 +920,7 @@ __global__ void __launch_bounds__((1 << (LOGN - 4)) * ROWS, 4) k_lde_pass1_rows(
 //     inside a row's work.  Row pitch = 8 (mod 32) words: the store phase's 8 rows x 8 positions per wavefront fall into 64
 //     different banks (the odd pitch of TVM_ROW_WORDS put b + j1 = const into one).
 // 8 rows, 512 work-items, 78 KB of LDS: two workgroups per CU.
-#define TVM_P2F_ROWW(logn) ((logn) == 8 ? 296 : (logn) == 9 ? 552 : (logn) == 10 ? 1096 : 2184)   // >= TVM_ROW_WORDS, = 8 (mod 32)
-#define TVM_P2F_TW2_WORDS 272   // 16 x 17: the middle group's twiddles
-#define TVM_P2F_LDS_WORDS(logn) (8 * TVM_P2F_ROWW(logn) + TVM_P2F_TW2_WORDS + TVM_ROW_WORDS(1 << (logn)) + 8)
-#define TVM_P2F_FLAG_WORDS 512   // u64 words in front of the tile at 2048 points: sixteen blocks of 64 pair flags (tvm_pair_sync)
-#define TVM_P2F_LDS_BYTES(logn) ((size_t)(TVM_P2F_LDS_WORDS(logn) + ((logn) == 11 ? TVM_P2F_FLAG_WORDS : 0)) * sizeof(u64))   // tile + twiddles + one coset's factors + a randomizer word per row: 79.2 / 159.4 KB
+// (the LDS layout, TVM_P2F_*: lde_plan.h)
 #ifndef TVM_P2F_FT_EARLY_11
 #define TVM_P2F_FT_EARLY_11 0   // (2048-point rows: the radix-8 last group leaves no registers for them)
 #endif
@@ -1129,51 +1123,67 @@ __global__ void k_pass2_fused_tables(const u64* __restrict__ lo, const u64* __re
 
 // ------------------------------------------------------------------------------------------------
 // host side
-// (the context's services -- pow_table, cached_table, scratch, the pool -- are context.hip's)
-static int threads_for_tile(int tile) {
-    int t = tile / 16;
-    t = (t + 63) / 64 * 64;
-    if (t < 64) t = 64;
-    if (t > 1024) t = 1024;
-    return t;
+// (the context's services -- pow_table, cached_table, scratch, the pool -- are context.hip's; which kernel runs a pass of
+// lde_table, and its launch shape, is lde_plan.h's)
+
+// Every kernel instantiation of the transforms, one row each, in the order of LdeKernel (lde_plan.h): a kernel is named HERE and
+// nowhere else -- taking its address instantiates it, set_lds_attributes() walks the rows, the launches look their kernel up.
+struct KernelVariant {
+    LdeKernel id;
+    void (*ntt2)(Ntt2Args);
+    void (*pass2)(LdePass2Args);
+    void (*pass3)(LdePass3Args);
+    bool raised_lds;   // may need more dynamic LDS than the 64 KiB a kernel gets without asking
+};
+constexpr KernelVariant variant(LdeKernel id, void (*k)(Ntt2Args), bool raised_lds) { return {id, k, nullptr, nullptr, raised_lds}; }
+constexpr KernelVariant variant(LdeKernel id, void (*k)(LdePass2Args), bool raised_lds) { return {id, nullptr, k, nullptr, raised_lds}; }
+constexpr KernelVariant variant(LdeKernel id, void (*k)(LdePass3Args), bool raised_lds) { return {id, nullptr, nullptr, k, raised_lds}; }
+static constexpr KernelVariant g_variants[] = {
+    variant(LdeKernel::ntt2_pass1, k_ntt2_pass1, true),
+    variant(LdeKernel::ntt2_pass2, k_ntt2_pass2, true),
+    variant(LdeKernel::lde_pass2, k_lde_pass2, true),
+    variant(LdeKernel::lde_pass3, k_lde_pass3, true),
+    variant(LdeKernel::pass1_rows_8_16, k_lde_pass1_rows<8, 16>, true),
+    variant(LdeKernel::pass1_rows_9_16, k_lde_pass1_rows<9, 16>, true),
+    variant(LdeKernel::pass1_rows_10_16, k_lde_pass1_rows<10, 16>, true),
+    variant(LdeKernel::pass1_rows_11_8, k_lde_pass1_rows<11, 8>, true),
+    variant(LdeKernel::pass2_fused_8, k_lde_pass2_fused<8>, true),
+    variant(LdeKernel::pass2_fused_9, k_lde_pass2_fused<9>, true),
+    variant(LdeKernel::pass2_fused_10, k_lde_pass2_fused<10>, true),
+    variant(LdeKernel::pass2_fused_11, k_lde_pass2_fused<11>, true),
+    variant(LdeKernel::pass2_v3_7_6, k_lde_pass2_v3<7, 6>, false),   // (the 64-work-item stand-ins: 9 / 10 KiB)
+    variant(LdeKernel::pass2_v3_8_6, k_lde_pass2_v3<8, 6>, false),
+    variant(LdeKernel::pass2_v3_11_10, k_lde_pass2_v3<11, 10>, true),
+    variant(LdeKernel::pass2_v3_12_10, k_lde_pass2_v3<12, 10>, true),
+    variant(LdeKernel::pass3_rows_8_8, k_lde_pass3_rows<8, 8>, true),
+    variant(LdeKernel::pass3_rows_9_8, k_lde_pass3_rows<9, 8>, true),
+    variant(LdeKernel::pass3_rows_10_8, k_lde_pass3_rows<10, 8>, true),
+    variant(LdeKernel::pass3_rows_11_8, k_lde_pass3_rows<11, 8>, true),
+    variant(LdeKernel::pass3_halves_8, k_lde_pass3_halves<8>, true),
+    variant(LdeKernel::pass3_v3_7_6, k_lde_pass3_v3<7, 6>, false),
+    variant(LdeKernel::pass3_v3_8_6, k_lde_pass3_v3<8, 6>, false),
+    variant(LdeKernel::pass3_v3_12_10, k_lde_pass3_v3<12, 10>, true),
+};
+constexpr bool variants_follow_the_enum() {
+    for (int i = 0; i < (int)(sizeof(g_variants) / sizeof(g_variants[0])); i++)
+        if ((int)g_variants[i].id != i) return false;
+    return true;
 }
-// Tile = 2^log_axis points x 2^batch transforms, at most 2^14 words = 128 KiB of LDS (one 1024-thread workgroup per
-// CU).  Measured alternative: 64 KiB tiles with two 512-thread workgroups per CU, so that one workgroup's global
-// traffic overlaps the other's butterflies -- no gain for the generic passes in round 1 (24.9 vs 25.5 ms for 128
-// columns), but worth 4 % for the LDE's pass 3 once its arithmetic had been trimmed (lde_table: k_lde_pass3_v3<10, 9>).
-static int tile_words_log() { return 14; }
-static int batch_log_for(int log_axis) {
-    int b = tile_words_log() - log_axis;
-    if (b < 0) b = 0;
-    return b > 4 ? 4 : b;
-}
+static_assert(sizeof(g_variants) / sizeof(g_variants[0]) == (size_t)LdeKernel::count && variants_follow_the_enum(),
+              "g_variants: one row per LdeKernel, in the enum's order");
+static const KernelVariant& variant_of(LdeKernel k) { return g_variants[(int)k]; }
 
 static bool g_attr_done = false;
 static void set_lds_attributes() {
     if (g_attr_done) return;
     g_attr_done = true;
     const int max_lds = 160 * 1024;
-    (void)hipFuncSetAttribute((const void*)k_ntt2_pass1, hipFuncAttributeMaxDynamicSharedMemorySize, max_lds);
-    (void)hipFuncSetAttribute((const void*)k_ntt2_pass2, hipFuncAttributeMaxDynamicSharedMemorySize, max_lds);
-    (void)hipFuncSetAttribute((const void*)k_lde_pass2, hipFuncAttributeMaxDynamicSharedMemorySize, max_lds);
-    (void)hipFuncSetAttribute((const void*)k_lde_pass3, hipFuncAttributeMaxDynamicSharedMemorySize, max_lds);
-    (void)hipFuncSetAttribute((const void*)k_lde_pass1_rows<8, 16>, hipFuncAttributeMaxDynamicSharedMemorySize, max_lds);
-    (void)hipFuncSetAttribute((const void*)k_lde_pass1_rows<9, 16>, hipFuncAttributeMaxDynamicSharedMemorySize, max_lds);
-    (void)hipFuncSetAttribute((const void*)k_lde_pass1_rows<10, 16>, hipFuncAttributeMaxDynamicSharedMemorySize, max_lds);
-    (void)hipFuncSetAttribute((const void*)k_lde_pass1_rows<11, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, max_lds);
-    (void)hipFuncSetAttribute((const void*)k_lde_pass2_fused<8>, hipFuncAttributeMaxDynamicSharedMemorySize, max_lds);
-    (void)hipFuncSetAttribute((const void*)k_lde_pass2_fused<9>, hipFuncAttributeMaxDynamicSharedMemorySize, max_lds);
-    (void)hipFuncSetAttribute((const void*)k_lde_pass2_fused<10>, hipFuncAttributeMaxDynamicSharedMemorySize, max_lds);
-    (void)hipFuncSetAttribute((const void*)k_lde_pass2_fused<11>, hipFuncAttributeMaxDynamicSharedMemorySize, max_lds);
-    (void)hipFuncSetAttribute((const void*)k_lde_pass3_rows<8, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, max_lds);
-    (void)hipFuncSetAttribute((const void*)k_lde_pass3_rows<9, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, max_lds);
-    (void)hipFuncSetAttribute((const void*)k_lde_pass3_rows<10, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, max_lds);
-    (void)hipFuncSetAttribute((const void*)k_lde_pass3_rows<11, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, max_lds);
-    (void)hipFuncSetAttribute((const void*)k_lde_pass3_halves<8>, hipFuncAttributeMaxDynamicSharedMemorySize, max_lds);
-    (void)hipFuncSetAttribute((const void*)k_lde_pass2_v3<11, 10>, hipFuncAttributeMaxDynamicSharedMemorySize, max_lds);
-    (void)hipFuncSetAttribute((const void*)k_lde_pass2_v3<12, 10>, hipFuncAttributeMaxDynamicSharedMemorySize, max_lds);
-    (void)hipFuncSetAttribute((const void*)k_lde_pass3_v3<12, 10>, hipFuncAttributeMaxDynamicSharedMemorySize, max_lds);
+    for (const KernelVariant& v : g_variants) {
+        const void* k = v.ntt2 ? (const void*)v.ntt2 : v.pass2 ? (const void*)v.pass2 : (const void*)v.pass3;
+        if (v.raised_lds) (void)hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, max_lds);
+    }
 }
+static unsigned tiles_of(u64 rows, int rows_per_tile) { return (unsigned)((rows + rows_per_tile - 1) / rows_per_tile); }
 
 // lo[k][i] = scale * gamma_k^i (i < n1), hi[k][i] = gamma_k^(n1*i) (i < n2), gamma_k = offset * gen^k
 __global__ void k_coset_tables(u64 offset, u64 gen, u64 X, u64 n1, u64 n2, u64 scale, u64* lo, u64* hi) {
@@ -1224,6 +1234,16 @@ static int pass2_fused_tables(tvm_ctx* c, u64 trace_gen, u64 offset, u64 gen, u6
     return TVM_OK;
 }
 
+// the table of k_lde_pass3_halves (2048-point rows as two 1024-point halves), cached per context: the second half's last-group factors
+static int pass3_halves_table(tvm_ctx* c, u64 w_2048, const u64* tw_2048, const u64** fb_tw) {
+    bool is_new = false;
+    u64* fb = cached_table(c, TableKind::Pass3Halves, w_2048, 2048, 0, 1024, &is_new);
+    if (!fb) return set_error(c, TVM_ERR_OUT_OF_MEMORY, "pass-3 twiddle table");
+    if (is_new) TVM_LAUNCH(k_pass3_halves_table, dim3(4), dim3(256), 0, c->stream, tw_2048, fb);
+    *fb_tw = fb;
+    return TVM_OK;
+}
+
 struct Split {
     int log_n, log_n1, log_n2, shift;
 };
@@ -1266,6 +1286,24 @@ static int classify_root(u64 w, u64 n) {
     return 0;
 }
 
+// What every two-pass transform fills the same way: the shape, the column step's twiddles for root w, the inter-pass twiddles;
+// no scaling, the identity output map, virtual column 0.  (in, out, tmp, in_len, the strides and field kinds, tw2 and root are
+// the caller's; so is the check of tw1.)
+static int ntt2_common(tvm_ctx* c, u64 w, u64 n, const Split& sp, Ntt2Args* a) {
+    a->log_n1 = sp.log_n1;
+    a->log_n2 = sp.log_n2;
+    a->batch_log = batch_log_for(sp.log_n1);
+    a->tmp_col_stride = n;
+    a->tw1 = pow_table(c, bfe_pow(w, 1ull << sp.log_n2), 1ull << sp.log_n1);
+    a->tw2 = nullptr;
+    TVM_TRY(make_inter(c, w, sp, &a->tw_inter));
+    a->pre_hi = a->pre_lo = a->post_lo = a->post_hi = nullptr;
+    a->out_mul = 1;
+    a->out_add = 0;
+    a->col0 = 0;
+    return TVM_OK;
+}
+
 // Transform `ncols` columns of length n with root `w` (w^n = 1; pass the inverse root for an
 // inverse transform).  in_scale/out_scale: optional x[i] *= in_scale^i and X[k] *= out_mult*out_scale^k.
 int ntt_columns(tvm_ctx* c, const u64* in, u64 in_len, int in_fk, u64 in_col_stride, u64* out, int out_fk,
@@ -1281,18 +1319,13 @@ int ntt_columns(tvm_ctx* c, const u64* in, u64 in_len, int in_fk, u64 in_col_str
     a.out = out;
     a.tmp = (u64*)scratch(c, Scratch::NttTemp, (size_t)ncols * n * sizeof(u64));
     if (!a.tmp) return set_error(c, TVM_ERR_OUT_OF_MEMORY, "ntt scratch");
-    a.log_n1 = sp.log_n1;
-    a.log_n2 = sp.log_n2;
+    TVM_TRY(ntt2_common(c, w, n, sp, &a));
     a.in_len = in_len;
     a.in_fk = in_fk;
     a.out_fk = out_fk;
     a.in_col_stride = in_col_stride;
-    a.tmp_col_stride = n;
     a.out_col_stride = out_col_stride;
-    a.tw1 = pow_table(c, bfe_pow(w, n2), n1);
     a.tw2 = pow_table(c, bfe_pow(w, n1), n2);
-    TVM_TRY(make_inter(c, w, sp, &a.tw_inter));
-    a.pre_hi = a.pre_lo = a.post_lo = a.post_hi = nullptr;
     if (in_scale != TVM_ONE) {
         a.pre_lo = pow_table(c, in_scale, n2);
         a.pre_hi = pow_table(c, bfe_pow(in_scale, n2), n1);
@@ -1306,25 +1339,34 @@ int ntt_columns(tvm_ctx* c, const u64* in, u64 in_len, int in_fk, u64 in_col_str
     if (!a.tw1 || !a.tw2) return set_error(c, TVM_ERR_OUT_OF_MEMORY, "tables");
     a.out_mul = out_mul;
     a.out_add = out_add;
-    a.col0 = 0;
     a.root = classify_root(w, n);
-    {
-        a.batch_log = batch_log_for(sp.log_n1);
-        const int B = 1 << a.batch_log;
-        const int tile = (int)n1 << a.batch_log;
-        dim3 grid((unsigned)((n2 + B - 1) / B), (unsigned)ncols);
-        TVM_LAUNCH(k_ntt2_pass1, grid, dim3(threads_for_tile(tile)), (size_t)tile * sizeof(u64), c->stream, a);
-    }
-    {
-        a.batch_log = batch_log_for(sp.log_n2);
-        const int B = 1 << a.batch_log;
-        const int tile = (int)n2 << a.batch_log;
-        dim3 grid((unsigned)((n1 + B - 1) / B), (unsigned)ncols);
-        const size_t lds = (size_t)B * (n2 + TVM_ROW_PAD) * sizeof(u64);
-        TVM_LAUNCH(k_ntt2_pass2, grid, dim3(threads_for_tile(tile)), lds, c->stream, a);
-    }
+    const LdePass s1 = lde_generic_pass(LdeKernel::ntt2_pass1, sp.log_n1, a.batch_log, 0);
+    TVM_LAUNCH(variant_of(s1.kernel).ntt2, dim3(tiles_of(n2, s1.rows), (unsigned)ncols), dim3(s1.block), s1.lds_bytes, c->stream, a);
+    a.batch_log = batch_log_for(sp.log_n2);
+    const LdePass s2 = lde_generic_pass(LdeKernel::ntt2_pass2, sp.log_n2, a.batch_log, TVM_ROW_PAD);
+    TVM_LAUNCH(variant_of(s2.kernel).ntt2, dim3(tiles_of(n1, s2.rows), (unsigned)ncols), dim3(s2.block), s2.lds_bytes, c->stream, a);
     TVM_HIP_CHECK(c, hipGetLastError());
     return TVM_OK;
+}
+
+// Columns per chunk of lde_table (chunk_cols <= 0: the caller leaves the choice to the context's option, and that to this policy).
+// range_cols: the virtual columns this call transforms.
+static int lde_chunk_columns(tvm_ctx* c, int chunk_cols, u64 X, u64 n_rows, int W, int range_cols, bool split) {
+    // columns per chunk: 96 while the chunk's intermediates (96 * (1 + X) * N words, from the pool: they count against the
+    // context's memory limit) stay below 32 GiB AND below a third of what the context can still obtain, else 32.  Measured at 2^20
+    // rows (main table, with 8 row tiles per pass-3 workgroup): 16 -> 48.0 ms, 32 -> 47.0, 96 -> 45.6, 192 -> 45.5, 379 -> 45.1; at 2^22
+    // rows (intermediate 25.8 GB; round 4, whole proof): 32 -> 836.9 ms, 64 -> 821.8, 96 -> 820.6; at 2^21 rows 398.1 -> 392.0 --
+    // 2 % that are not worth the coset-wise fallback on a device (or under a limit) that 25.8 GB push over the edge.
+    // c->lde_chunk_columns (TVM_OPTION_LDE_CHUNK_COLUMNS) overrides.
+    const auto intermediates = [&](int cols) { return (size_t)cols * (1 + X) * n_rows * sizeof(u64); };
+    if (chunk_cols <= 0) chunk_cols = c->lde_chunk_columns;
+    // (short traces: every column in ONE chunk while its intermediates stay below 512 MB -- traces of up to 2^14 rows: three launches per
+    // table instead of twelve, and grids four times as wide on a chip they do not fill)
+    if (chunk_cols <= 0 && !split && intermediates(W) <= ((size_t)512 << 20)) chunk_cols = W > 96 ? W : 96;
+    if (chunk_cols <= 0) chunk_cols = (intermediates(96) <= ((size_t)36 << 30) && intermediates(96) <= pool_available(c, nullptr) / 3) ? 96 : 32;
+    // (a chunk wider than the columns there are buys nothing; not below 96, so that narrow tables keep sharing the blocks of the wide ones)
+    if (chunk_cols > 96 && chunk_cols > range_cols) chunk_cols = range_cols > 96 ? range_cols : 96;
+    return chunk_cols;
 }
 
 // master_table.rs:258-322.  trace: column-major [n_cols][n_rows][fk]; rnd: [n_cols][h][fk];
@@ -1352,43 +1394,23 @@ int lde_table(tvm_ctx* c, int fk, const u64* trace, u64 n_rows, u64 n_cols, cons
     const int first = split ? split->first_vcol : 0, last = split ? split->first_vcol + split->n_vcols : W;
     if (split && (first < 0 || split->n_vcols < 0 || last > W || !split->coeffs || (mode != TVM_LDE_INVERSE_ONLY && mode != TVM_LDE_FORWARD_ONLY)))
         return set_error(c, TVM_ERR_INVALID_ARGUMENT, "lde: column range / mode of the split");
-    // columns per chunk: 96 while the chunk's intermediates (96 * (1 + X) * N words, from the pool: they count against the
-    // context's memory limit) stay below 32 GiB AND below a third of what the context can still obtain, else 32.  Measured at 2^20
-    // rows (main table, with 8 row tiles per pass-3 workgroup): 16 -> 48.0 ms, 32 -> 47.0, 96 -> 45.6, 192 -> 45.5, 379 -> 45.1; at 2^22
-    // rows (intermediate 25.8 GB; round 4, whole proof): 32 -> 836.9 ms, 64 -> 821.8, 96 -> 820.6; at 2^21 rows 398.1 -> 392.0 --
-    // 2 % that are not worth the coset-wise fallback on a device (or under a limit) that 25.8 GB push over the edge.
-    // c->lde_chunk_columns (TVM_OPTION_LDE_CHUNK_COLUMNS) overrides.
-    const auto intermediates = [&](int cols) { return (size_t)cols * (1 + X) * n_rows * sizeof(u64); };
-    if (chunk_cols <= 0) chunk_cols = c->lde_chunk_columns;
-    // (short traces: every column in ONE chunk while its intermediates stay below 512 MB -- traces of up to 2^14 rows: three launches per
-    // table instead of twelve, and grids four times as wide on a chip they do not fill)
-    if (chunk_cols <= 0 && !split && intermediates(W) <= ((size_t)512 << 20)) chunk_cols = W > 96 ? W : 96;
-    if (chunk_cols <= 0) chunk_cols = (intermediates(96) <= ((size_t)36 << 30) && intermediates(96) <= pool_available(c, nullptr) / 3) ? 96 : 32;
-    // (a chunk wider than the columns there are buys nothing; not below 96, so that narrow tables keep sharing the blocks of the wide ones)
-    if (chunk_cols > 96 && chunk_cols > last - first) chunk_cols = last - first > 96 ? last - first : 96;
 
     const u64 w = trace_gen, wi = bfe_inv(trace_gen);
+    const bool std_roots = classify_root(w, N) == 1;  // every ArithmeticDomain's generator is; any other root takes the generic kernels
+    const LdePlan plan = lde_plan({sp.log_n, X, h, std_roots, c->lde_pass2_tiles, mode});
+    if (plan.pass3.grid_y >= 65536) return set_error(c, TVM_ERR_UNSUPPORTED, "lde: too many row tiles");
+    chunk_cols = lde_chunk_columns(c, chunk_cols, X, N, W, last - first, split != nullptr);
+
     const u64 n_inv = bfe_inv(bfe_from_u64(N));
     Ntt2Args p1;
     p1.in = trace;
     p1.out = nullptr;
-    p1.log_n1 = sp.log_n1;
-    p1.log_n2 = sp.log_n2;
-    p1.batch_log = batch_log_for(sp.log_n1);
+    TVM_TRY(ntt2_common(c, wi, N, sp, &p1));
     p1.in_len = N;
     p1.in_fk = fk;
     p1.out_fk = 1;
     p1.in_col_stride = N * fk;
-    p1.tmp_col_stride = N;
     p1.out_col_stride = 0;
-    p1.tw1 = pow_table(c, bfe_pow(wi, n2), n1);
-    p1.tw2 = nullptr;
-    TVM_TRY(make_inter(c, wi, sp, &p1.tw_inter));
-    p1.pre_hi = p1.pre_lo = p1.post_lo = p1.post_hi = nullptr;
-    p1.out_mul = 1;
-    p1.out_add = 0;
-    p1.col0 = 0;
-    const bool std_roots = classify_root(w, N) == 1;  // every ArithmeticDomain's generator is; any other root takes the generic kernels
     p1.root = std_roots ? 2 : 0;
 
     LdePass2Args p2;
@@ -1407,10 +1429,7 @@ int lde_table(tvm_ctx* c, int fk, const u64* trace, u64 n_rows, u64 n_cols, cons
     p2.g_lo_step = pow_table(c, eval_gen, n1);
     p2.g_hi_step = pow_table(c, bfe_pow(eval_gen, n1), n2);
     p2.g_hi_pos = p2.f_tw = p2.u_tw = nullptr;
-    // (256- and 512-point axes -- 2^16 .. 2^19-row traces -- since round 6; TVM_OPTION_LDE_PASS2_TILES restores the tile kernels on all of them)
-    const bool short_rows = c->lde_pass2_tiles == 0;   // the row kernels of passes 1 and 3 on 256- / 512-point axes, likewise
-    const bool fused = std_roots && sp.log_n2 >= 8 && sp.log_n2 <= 11 && n1 % 16 == 0 && h <= n1 && c->lde_pass2_tiles == 0;
-    if (fused)
+    if (is_pass2_fused(plan.pass2.kernel))
         TVM_TRY(pass2_fused_tables(c, w, eval_offset, eval_gen, X, sp.log_n1, sp.log_n2, p2.g_lo, p2.g_hi, p2.tw_inter, p2.tw_b1, &p2.g_hi_pos,
                                    &p2.f_tw, &p2.u_tw));
     const u64 n_mont = bfe_from_u64(N);
@@ -1425,14 +1444,17 @@ int lde_table(tvm_ctx* c, int fk, const u64* trace, u64 n_rows, u64 n_cols, cons
     p3.log_n1 = sp.log_n1;
     p3.log_n2 = sp.log_n2;
     p3.n_cosets = (int)X;
+    p3.tiles = plan.pass3.tiles;
     p3.L = L;
     p3.W = W;
     p3.pitch = lde_table_layout(N, L).pitch;
+    p3.rows_log = batch_log_for(sp.log_n1);
     p3.std_roots = std_roots ? 1 : 0;
     p3.tw_b2 = pow_table(c, bfe_pow(w, n2), n1);
     p3.fb_tw = nullptr;
     if (!p1.tw1 || !p2.tw_a2 || !p2.tw_b1 || !p2.g_lo || !p2.g_hi || !p2.g_lo_step || !p2.g_hi_step || !p3.tw_b2)
         return set_error(c, TVM_ERR_OUT_OF_MEMORY, "lde tables");
+    if (plan.pass3.kernel == LdeKernel::pass3_halves_8) TVM_TRY(pass3_halves_table(c, bfe_pow(w, n2), p3.tw_b2, &p3.fb_tw));
 
     // the intermediates of one chunk: Y (pass 1 -> pass 2) and Z (pass 2 -> pass 3), pool blocks (the next call of the same
     // shape gets the same blocks back from the cache, in stream order)
@@ -1455,117 +1477,31 @@ int lde_table(tvm_ctx* c, int fk, const u64* trace, u64 n_rows, u64 n_cols, cons
         const int nc = (last - col0 < chunk_cols) ? (last - col0) : chunk_cols;
         p1.tmp = split ? y + (size_t)(col0 - first) * N : y;
         p2.y = p1.tmp;
-        if (mode != TVM_LDE_FORWARD_ONLY) {
+        if (plan.pass1.kernel != LdeKernel::none) {
+            const LdePass& s = plan.pass1;
             Ntt2Args a = p1;
             a.col0 = col0;
-            const int B = 1 << a.batch_log;
-            const int tile = (int)n1 << a.batch_log;
-            dim3 grid((unsigned)((n2 + B - 1) / B), (unsigned)nc);
-            if (std_roots && short_rows && (sp.log_n1 == 8 || sp.log_n1 == 9) && n2 % 16 == 0) {   // 256 / 512 points: four / two rows per wavefront
-                const size_t lds_r = (size_t)(16 * TVM_ROW_WORDS(n1) + n1) * sizeof(u64);
-                if (sp.log_n1 == 8) TVM_LAUNCH((k_lde_pass1_rows<8, 16>), dim3((unsigned)(n2 / 16), (unsigned)nc), dim3(256), lds_r, c->stream, a);
-                else TVM_LAUNCH((k_lde_pass1_rows<9, 16>), dim3((unsigned)(n2 / 16), (unsigned)nc), dim3(512), lds_r, c->stream, a);
-            } else
-            if (std_roots && sp.log_n1 == 10 && n2 % 16 == 0) {   // 1024-point axis: one row per wavefront
-                // 16-row tiles: 128-byte runs of the input.  (8-row tiles -- two workgroups per CU -- measured the same time and
-                // fetch every input line twice: 16 instead of 8 B per cell, profiles/r03_q_pmc_lde.txt.)
-                const size_t lds_r = (size_t)(16 * TVM_ROW_WORDS(n1) + n1) * sizeof(u64);
-                TVM_LAUNCH((k_lde_pass1_rows<10, 16>), dim3((unsigned)(n2 / 16), (unsigned)nc), dim3(1024), lds_r, c->stream, a);
-            } else if (std_roots && sp.log_n1 == 11 && n2 % 8 == 0 && c->lde_pass2_tiles == 0) {   // 2048-point axis: two wavefronts per row
-                const size_t lds_r = (size_t)(8 * TVM_ROW_WORDS(n1) + n1 + 512) * sizeof(u64);   // (+ sixteen blocks of 64 pair flags)
-                TVM_LAUNCH((k_lde_pass1_rows<11, 8>), dim3((unsigned)(n2 / 8), (unsigned)nc), dim3(1024), lds_r, c->stream, a);
-            } else
-                TVM_LAUNCH(k_ntt2_pass1, grid, dim3(threads_for_tile(tile)), (size_t)tile * sizeof(u64), c->stream, a);
+            TVM_LAUNCH(variant_of(s.kernel).ntt2, dim3(tiles_of(n2, s.rows), (unsigned)nc), dim3(s.block), s.lds_bytes, c->stream, a);
         }
         {
+            LdePass s = plan.pass2;
             LdePass2Args a = p2;
             a.col0 = col0;
-            const int B = 1 << a.batch_log;
-            const int tile = (int)n2 << a.batch_log;
-            dim3 grid((unsigned)((n1 + B - 1) / B), (unsigned)nc);
-            const size_t lds = (size_t)B * (n2 + TVM_ROW_PAD) * sizeof(u64);
-            // axes longer than a workgroup: 2048 / 4096 points on 1024 work-items (2^21 .. 2^24 rows), and the same shapes at a
-            // size the CPU suite can run (128 / 256 points on 64 work-items); rows per tile = 16 / positions per work-item
-            const int ppt_log = (sp.log_n2 == 11 || sp.log_n2 == 7) ? 1 : (sp.log_n2 == 12 || sp.log_n2 == 8) ? 2 : 0;
-            const u64 rows3 = 16 >> ppt_log;
-            const size_t lds_v3 = (size_t)(rows3 * (n2 + TVM_ROW_PAD) + (sp.log_n2 < 12 ? n2 : 0) + 32) * sizeof(u64);
-            const dim3 g2((unsigned)(n1 / rows3), (unsigned)nc);
-            if (fused) {
-                // 1024- / 2048-point axis: every wavefront (pair of wavefronts) keeps its row across the coset loop (k_lde_pass2_fused);
-                // more trace randomizers than n1 (never the case for a STARK's parameters) take the kernels below
-                const size_t lds_r = TVM_P2F_LDS_BYTES(sp.log_n2);
-                if (sp.log_n2 == 8) TVM_LAUNCH((k_lde_pass2_fused<8>), dim3((unsigned)(n1 / 8), (unsigned)nc), dim3(128), lds_r, c->stream, a);
-                else if (sp.log_n2 == 9) TVM_LAUNCH((k_lde_pass2_fused<9>), dim3((unsigned)(n1 / 8), (unsigned)nc), dim3(256), lds_r, c->stream, a);
-                else if (sp.log_n2 == 10) TVM_LAUNCH((k_lde_pass2_fused<10>), dim3((unsigned)(n1 / 8), (unsigned)nc), dim3(512), lds_r, c->stream, a);
-                else TVM_LAUNCH((k_lde_pass2_fused<11>), dim3((unsigned)(n1 / 8), (unsigned)nc), dim3(1024), lds_r, c->stream, a);
-            }
-            else if (std_roots && ppt_log && n1 % rows3 == 0) {
-                if (sp.log_n2 == 11) TVM_LAUNCH((k_lde_pass2_v3<11, 10>), g2, dim3(1024), lds_v3, c->stream, a);
-                else if (sp.log_n2 == 12) TVM_LAUNCH((k_lde_pass2_v3<12, 10>), g2, dim3(1024), lds_v3, c->stream, a);
-                else if (sp.log_n2 == 7) TVM_LAUNCH((k_lde_pass2_v3<7, 6>), g2, dim3(64), lds_v3, c->stream, a);
-                else TVM_LAUNCH((k_lde_pass2_v3<8, 6>), g2, dim3(64), lds_v3, c->stream, a);
-            }
-            else {
-                // Short axes (traces below 2^13 rows): a 16-row tile is ONE wavefront that walks its 16 coefficients per lane through
-                // nine transforms, and the grid is n1 / 16 x columns of them -- 384 wavefronts for 96 columns of a 2^12-row trace, 200 us
-                // of latency.  Fewer rows per tile until the grid has ~2048 wavefronts (or a tile is two rows): the same kernel, the
-                // same words (the tile height is a launch shape: every row is transformed on its own), 200 -> 60 us.
-                int bl = a.batch_log;
-                const auto waves = [&](int b) { return (u64)((n1 + (1u << b) - 1) >> b) * (u64)nc * (u64)(threads_for_tile((int)n2 << b) / 64); };
-                while (bl > 1 && waves(bl) < 2048) bl--;
-                a.batch_log = bl;
-                const int tile_s = (int)n2 << bl;
-                const dim3 grid_s((unsigned)((n1 + (1u << bl) - 1) >> bl), (unsigned)nc);
-                const size_t lds_s = ((size_t)(n2 + TVM_ROW_PAD) << bl) * sizeof(u64);
-                TVM_LAUNCH(k_lde_pass2, grid_s, dim3(threads_for_tile(tile_s)), lds_s, c->stream, a);
-            }
+            // Short axes (traces below 2^13 rows) on the generic kernel: a 16-row tile is ONE wavefront that walks its 16 coefficients per
+            // lane through nine transforms, and the grid is n1 / 16 x columns of them -- 384 wavefronts for 96 columns of a 2^12-row
+            // trace, 200 us of latency.  Fewer rows per tile until the grid has ~2048 wavefronts (or a tile is two rows): the same
+            // kernel, the same words (the tile height is a launch shape: every row is transformed on its own), 200 -> 60 us.
+            const auto waves = [&](const LdePass& g) { return (u64)tiles_of(n1, g.rows) * (u64)nc * (u64)(g.block / 64); };
+            while (s.kernel == LdeKernel::lde_pass2 && a.batch_log > 1 && waves(s) < 2048)
+                s = lde_generic_pass(s.kernel, sp.log_n2, --a.batch_log, TVM_ROW_PAD);
+            TVM_LAUNCH(variant_of(s.kernel).pass2, dim3(tiles_of(n1, s.rows), (unsigned)nc), dim3(s.block), s.lds_bytes, c->stream, a);
         }
-        if (mode != TVM_LDE_INVERSE_ONLY) {
+        if (plan.pass3.kernel != LdeKernel::none) {
+            const LdePass& s = plan.pass3;
             LdePass3Args a = p3;
             a.col0 = col0;
-            a.rows_log = batch_log_for(sp.log_n1);
-            const int RB = 1 << a.rows_log;
-            const int tile = (int)n1 << a.rows_log;
-            dim3 grid((unsigned)((X * n2 + RB - 1) / RB), (unsigned)nc);
-            const size_t lds = ((size_t)(n1 + TVM_ROW_PAD) << a.rows_log) * sizeof(u64);
-            const int ppt_log = (sp.log_n1 == 11 || sp.log_n1 == 7) ? 1 : (sp.log_n1 == 12 || sp.log_n1 == 8) ? 2 : 0;
-            const u64 rows3 = 16 >> ppt_log, tiles3 = X * n2 / rows3;  // see pass 2
-            // (pass 3 has no coset loop and no workgroup barrier: here the 2048-point row form is 8 % faster than k_lde_pass3_v3<11, 10>,
-            // 15.5 against 16.8 ms per 96 columns at 2^22 rows, even at two wavefronts per SIMD)
-            if (std_roots && (sp.log_n1 == 10 || sp.log_n1 == 11 || (short_rows && (sp.log_n1 == 8 || sp.log_n1 == 9))) && (X * n2) % 8 == 0) {
-                // 1024- / 2048-point axis: one (k, j1) row per wavefront, no workgroup barrier (k_lde_pass3_rows): 8 wavefronts per
-                // workgroup -- 78 KB of LDS, two workgroups per CU at 1024 points (4 wavefronts per workgroup: +2 %, 16: +3 %,
-                // profiles/r03_g_lde_ab.txt); one workgroup per CU at 2048
-                const u64 tiles_w = X * n2 / 8;
-                a.tiles = tiles_w % 16 == 0 ? 16 : tiles_w % 8 == 0 ? 8 : tiles_w % 4 == 0 ? 4 : 1;
-                if (tiles_w / a.tiles >= 65536) return set_error(c, TVM_ERR_UNSUPPORTED, "lde: too many row tiles");
-                const size_t lds_w = (size_t)(8 * TVM_ROW_WORDS(n1) + n1) * sizeof(u64);
-                const dim3 g3((unsigned)nc, (unsigned)(tiles_w / a.tiles));
-                if (sp.log_n1 == 11 && c->lde_pass2_tiles == 0) {
-                    // 2048-point rows as two 1024-point halves through one LDS region per wavefront (k_lde_pass3_halves)
-                    bool is_new = false;
-                    u64* fb = cached_table(c, TableKind::Pass3Halves, bfe_pow(w, n2), 2048, 0, 1024, &is_new);
-                    if (!fb) return set_error(c, TVM_ERR_OUT_OF_MEMORY, "pass-3 twiddle table");
-                    if (is_new) TVM_LAUNCH(k_pass3_halves_table, dim3(4), dim3(256), 0, c->stream, a.tw_b2, fb);
-                    a.fb_tw = fb;
-                    const size_t lds_h = (size_t)(8 * TVM_ROW_WORDS(1024) + 1024) * sizeof(u64);
-                    TVM_LAUNCH((k_lde_pass3_halves<8>), g3, dim3(512), lds_h, c->stream, a);
-                } else if (sp.log_n1 == 11) TVM_LAUNCH((k_lde_pass3_rows<11, 8>), g3, dim3(512), lds_w, c->stream, a);
-                else if (sp.log_n1 == 8) TVM_LAUNCH((k_lde_pass3_rows<8, 8>), g3, dim3(512), lds_w, c->stream, a);
-                else if (sp.log_n1 == 9) TVM_LAUNCH((k_lde_pass3_rows<9, 8>), g3, dim3(512), lds_w, c->stream, a);
-                else TVM_LAUNCH((k_lde_pass3_rows<10, 8>), g3, dim3(512), lds_w, c->stream, a);
-            } else
-            if (std_roots && ppt_log && (X * n2) % 16 == 0) {
-                a.tiles = tiles3 % 8 == 0 ? 8 : tiles3 % 4 == 0 ? 4 : 1;
-                const dim3 g3((unsigned)nc, (unsigned)(tiles3 / a.tiles));
-                const size_t lds_v3 = (size_t)(rows3 * (n1 + TVM_ROW_PAD) + (sp.log_n1 < 12 ? n1 : 0)) * sizeof(u64);
-                if (g3.y >= 65536) return set_error(c, TVM_ERR_UNSUPPORTED, "lde: too many row tiles");
-                if (sp.log_n1 == 12) TVM_LAUNCH((k_lde_pass3_v3<12, 10>), g3, dim3(1024), lds_v3, c->stream, a);
-                else if (sp.log_n1 == 7) TVM_LAUNCH((k_lde_pass3_v3<7, 6>), g3, dim3(64), lds_v3, c->stream, a);
-                else TVM_LAUNCH((k_lde_pass3_v3<8, 6>), g3, dim3(64), lds_v3, c->stream, a);
-            }
-            else
-                TVM_LAUNCH(k_lde_pass3, grid, dim3(threads_for_tile(tile)), lds, c->stream, a);
+            const dim3 grid = s.grid_y ? dim3((unsigned)nc, (unsigned)s.grid_y) : dim3(tiles_of(X * n2, s.rows), (unsigned)nc);
+            TVM_LAUNCH(variant_of(s.kernel).pass3, grid, dim3(s.block), s.lds_bytes, c->stream, a);
         }
     }
     TVM_HIP_CHECK(c, hipGetLastError());
