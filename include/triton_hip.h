@@ -411,6 +411,54 @@ int32_t tvm_table_linear_combination(tvm_ctx* ctx, const tvm_table* table, uint6
 int32_t tvm_deep_codeword(tvm_ctx* ctx, uint32_t n_components, const uint64_t* const* d_codewords, tvm_domain domain,
                           const uint64_t* h_points, const uint64_t* h_values, const uint64_t* h_weights,
                           uint64_t* d_out);
+/* The same with the three small arrays in device memory (n_components XFE each), where earlier kernels of the stream may have left
+ * them: nothing is copied, nothing waits (csrc/proof_middle.hip: k_deep_dev, k_deep_short_dev). */
+int32_t tvm_deep_codeword_device_args(tvm_ctx* ctx, uint32_t n_components, const uint64_t* const* d_codewords, tvm_domain domain,
+                                      const uint64_t* d_points, const uint64_t* d_values, const uint64_t* d_weights,
+                                      uint64_t* d_out);
+
+/* ---- the PROOF MIDDLE: from the quotient's Merkle root to the DEEP codeword (Prover::prove steps 12-16, stark.rs:444-639) with the
+ * transcript on the device, without the host in between (csrc/proof_middle.hip) ------------------------------
+ * d_main_trace [n_main_cols][n_rows] words and d_aux_trace [n_aux_cols][n_rows][3] with their trace randomizers ([cols][h] elements),
+ * column-major as tvm_out_of_domain_rows takes them, over trace_domain (offset 1, length n_rows); d_polys: the five segment
+ * polynomials [5][poly_len] XFE and `segments` their table, as tvm_quotient_segments made them; d_quotient_nodes: the tree over that
+ * table (tvm_table_merkle_tree), or null when h_sponge_state already holds the quotient root; short_domain: the shorter of the
+ * quotient and the LDT domain, at most the table's rows; zeta: Stark::ZETA.  On the stream, in the order of Prover::prove:
+ *     ProofItem::MerkleRoot(d_quotient_nodes[1]) absorbed (where given); sample_scalars(1) = alpha            stark.rs:444-452
+ *     the points alpha, alpha * trace_domain.generator, alpha^4, (zeta alpha)^4                                stark.rs:454-476
+ *     the out-of-domain rows of both tables at the first two (tvm_out_of_domain_rows), the five segment
+ *     polynomials at the last two (tvm_evaluate_polys_at_points)                                               stark.rs:456-476
+ *     the six out-of-domain items absorbed (main row, aux row, main next row, aux next row, segments 0..3 at
+ *     alpha^4, segments 1..4 at (zeta alpha)^4); sample_scalars(3) = w0, w1, w2                                stark.rs:478-505
+ *     the weighted sum of all columns with the powers of w0 (tvm_weighted_sum_of_columns of both tables, added),
+ *     its codeword on short_domain and its values at alpha and alpha * generator; the segment combinations with
+ *     (w1^0..w1^3, 0) and (0, w1^1..w1^4) on short_domain (tvm_table_linear_combination) and their values    stark.rs:507-543
+ *     d_combination (short_domain.length XFE) = tvm_deep_codeword of those four with the weights w2^0..w2^3   stark.rs:545-625
+ * h_block receives TVM_MIDDLE_BLOCK_WORDS(n_main_cols, n_aux_cols) words (block_capacity: at least that many), at the offsets
+ * below.  The caller enqueues the root and the six items from it and replays both samplings on its own sponge, which must arrive at
+ * the same alpha, w0..w2 and state.  ONE stream synchronisation, at the end.  On bad arguments nothing is queued. */
+#define TVM_MIDDLE_ROOT 0u                                                  /* [5]; zeros without a tree */
+#define TVM_MIDDLE_POINTS 5u                                                /* [4][3]: alpha, alpha * omega, alpha^4, (zeta alpha)^4 */
+#define TVM_MIDDLE_MAIN_ROWS 17u                                            /* [2][n_main][3]: the row at alpha, the next row */
+#define TVM_MIDDLE_AUX_ROWS(n_main) (17u + 6u * (n_main))                   /* [2][n_aux][3] */
+#define TVM_MIDDLE_SEGMENTS(n_main, n_aux) (17u + 6u * ((n_main) + (n_aux))) /* [5][2][3]: polynomial k at alpha^4, (zeta alpha)^4 */
+#define TVM_MIDDLE_VALUES(n_main, n_aux) (TVM_MIDDLE_SEGMENTS(n_main, n_aux) + 30u)   /* [4][3]: the DEEP values */
+#define TVM_MIDDLE_WEIGHTS(n_main, n_aux) (TVM_MIDDLE_VALUES(n_main, n_aux) + 12u)    /* [3][3]: w0, w1, w2 */
+#define TVM_MIDDLE_STATE(n_main, n_aux) (TVM_MIDDLE_WEIGHTS(n_main, n_aux) + 9u)      /* [16]: the sponge afterwards */
+#define TVM_MIDDLE_BLOCK_WORDS(n_main, n_aux) (TVM_MIDDLE_STATE(n_main, n_aux) + 16u)
+int32_t tvm_out_of_domain_to_deep(tvm_ctx* ctx, const uint64_t* d_main_trace, uint64_t n_main_cols, const uint64_t* d_main_randomizers,
+                                  const uint64_t* d_aux_trace, uint64_t n_aux_cols, const uint64_t* d_aux_randomizers, uint64_t n_rows,
+                                  uint64_t num_trace_randomizers, tvm_domain trace_domain, const uint64_t* d_polys, uint64_t poly_len,
+                                  const tvm_table* segments, const uint64_t* d_quotient_nodes, tvm_domain short_domain, uint64_t zeta,
+                                  const uint64_t* h_sponge_state, uint64_t* d_combination, uint64_t* h_block, uint64_t block_capacity);
+uint64_t tvm_out_of_domain_to_deep_block_words(uint64_t n_main_cols, uint64_t n_aux_cols);   /* TVM_MIDDLE_BLOCK_WORDS */
+/* The weight vectors of steps 14-15 alone, as tvm_out_of_domain_to_deep forms them on the device (k_weight_vectors), from host arrays
+ * (an entry point of its own, as tvm_sponge_sample_indices is).  h_scalars [3][3]: w0, w1, w2; h_segments [5][2][3]: the segment
+ * polynomials at the two points.  h_w_columns [n_columns][3] = w0^0 .. w0^(n_columns - 1); h_wp [5][3] = (w1^0 .. w1^3, 0);
+ * h_wr [5][3] = (0, w1^1 .. w1^4); h_wd [4][3] = w2^0 .. w2^3; h_pr_values [2][3] = sum_{k<4} w1^k segments[k][0],
+ * sum_{1<=k<5} w1^k segments[k][1].  One launch, one synchronisation. */
+int32_t tvm_combination_weight_vectors(tvm_ctx* ctx, const uint64_t* h_scalars, const uint64_t* h_segments, uint32_t n_columns,
+                                       uint64_t* h_w_columns, uint64_t* h_wp, uint64_t* h_wr, uint64_t* h_wd, uint64_t* h_pr_values);
 
 /* ---- the PROOF TAIL: what follows the commit phase of Fri::prove (fri.rs:265-319) and the trace openings of Prover::prove
  * (stark.rs:665-716) with the transcript on the device (csrc/proof_tail.hip) ------------------------------------

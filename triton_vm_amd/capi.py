@@ -124,6 +124,13 @@ _SIGNATURES = {
     "tvm_table_linear_combination": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
     "tvm_deep_codeword": (C.c_int32, [C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p), Domain, C.c_void_p, C.c_void_p,
                                       C.c_void_p, C.c_void_p]),
+    "tvm_deep_codeword_device_args": (C.c_int32, [C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p), Domain, C.c_void_p, C.c_void_p,
+                                                  C.c_void_p, C.c_void_p]),
+    "tvm_out_of_domain_to_deep": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64,
+                                              C.c_uint64, Domain, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, Domain, C.c_uint64,
+                                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]),
+    "tvm_out_of_domain_to_deep_block_words": (C.c_uint64, [C.c_uint64, C.c_uint64]),
+    "tvm_combination_weight_vectors": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32] + [C.c_void_p] * 5),
     "tvm_fri_split_and_fold": (C.c_int32, [C.c_void_p, C.c_void_p, Domain, C.c_void_p, C.c_void_p]),
     "tvm_stir_merkle_tree": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p]),
     "tvm_fold_polynomial": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p]),

@@ -147,6 +147,8 @@ enum class Scratch : int {
     AirCheckListed,         // ... the failing rows
     AirCheckPairIndices,    // ... pinpointing: rows r, r + 1 of a batch of listed rows
     AirCheckPairs,          // ... and their words
+    MiddleBlock,            // tvm_out_of_domain_to_deep: the block that goes back to the host and the weight vectors behind it, held
+                            // across out_of_domain_rows, poly_eval, ntt_columns (unit slots) and tvm_evaluate (helper and unit slots)
     Count
 };
 // The kinds of constant table a context caches (cached_table); what the three key words mean is the kind's own business:

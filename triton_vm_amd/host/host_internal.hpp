@@ -130,10 +130,18 @@ protected:
     // TVMH_OPTION_DEVICE_TAIL: the three tables (main, aux, quotient segments) extended over the whole LDT domain and their whole
     // trees, where this prover has them (the single-GPU one); false: the proof's tail keeps the host's path
     virtual bool whole_tables_and_trees(const tvm_table* /*tables*/[3], const u64* /*trees*/[3]) { return false; }
+    // TVMH_OPTION_DEVICE_MIDDLE: commit(QUOT, ..) without fetching the root, where this prover has the whole traces and builds the whole
+    // quotient tree (the single-GPU one) -> the tree's nodes on the device; null, and nothing done: the proof's middle keeps the host's path
+    virtual const u64* commit_whole_quotient_tree(const tvm_table* /*segments*/) { return nullptr; }
 
 private:
     std::vector<u64> fri(DeviceBuffer&& combination);   // -> the first-round indices
     bool fri_device_tail(const std::vector<FriRound>& rounds, std::vector<u64>& a_indices);
+    // 13-16 on this rank's rows of the short domain -> the DEEP codeword; a4: the point alpha^4, which step 18 checks.  host_middle: the
+    // host in the loop; device_middle: the quotient root and 13-16 in one device round trip (false: does not apply, nothing was done)
+    DeviceBuffer host_middle(const tvm_table* segments, const DeviceBuffer& polys, u64 poly_len, const ArithmeticDomain& short_rank, u64 zeta, Xfe& a4);
+    bool device_middle(const tvm_table* segments, const DeviceBuffer& polys, u64 poly_len, const ArithmeticDomain& short_dom, u64 zeta, Xfe& a4,
+                       DeviceBuffer& combination);
     Openings tail_openings;   // the openings of step 19 when fri_device_tail has fetched them
     bool have_tail_openings = false;
 };

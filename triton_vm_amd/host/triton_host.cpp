@@ -636,50 +636,18 @@ void ProofSteps::segment_combinations(const tvm_table* segments, const DeviceBuf
     c.check(tvm_table_linear_combination(c.raw(), segments, short_rank.length, wr->c, cw_r.ptr()), "tvm_table_linear_combination");
 }
 
-ProofStream ProofSteps::prove() {
-    ps.alter_fiat_shamir_state_with(claim.encode());  // stark.rs:336-339
-    {
-        const u64 log2_padded_height = to_mont(bit_length(p.padded_height) - 1);  // stark.rs:354
-        ps.enqueue("log2 padded height", &log2_padded_height, 1);
-    }
-    const u64 L = p.ldt.length;
-    const ArithmeticDomain short_dom = p.ldt.length <= p.quotient.length ? p.ldt : p.quotient;
-    const ArithmeticDomain ldt_rank = local(p.ldt), short_rank = local(short_dom);   // (one rank: the domains themselves)
-    const u64 zeta = to_mont(3);  // Stark::ZETA, stark.rs:1801
+// Steps 13-16 of prove() with the host in the loop: five stream-draining round trips (the two out-of-domain row calls, the segment
+// values, the combination's values; the quotient root before them), the transcript and the weight vectors on the host in between.
+DeviceBuffer ProofSteps::host_middle(const tvm_table* segments, const DeviceBuffer& polys, u64 poly_len, const ArithmeticDomain& short_rank, u64 zeta,
+                                     Xfe& a4) {
     auto enqueue_xfes = [&](const char* name, const std::vector<Xfe>& v) { ps.enqueue(name, v[0].c, 3 * v.size()); };
-
-    // 4-6: main table LDE, Merkle tree, challenges  (stark.rs:367-377)
-    mark("main LDE");
-    extend_master_table(MAIN);
-    mark("main Merkle");
-    ps.enqueue("main root", commit(MAIN, nullptr).data(), 5);
-    const std::vector<Xfe> challenges = derive_challenges(ps.sample_scalars(NUM_SAMPLED_CHALLENGES), claim);
-    mark("extend");
-    if (extend) extend(challenges);  // MasterMainTable::extend (stark.rs:379-381); over ranks: replicated
-
-    // 8-9: aux table (its `extend` is host work in the reference; the trace is already resident)
-    mark("aux LDE");
-    extend_master_table(AUX);
-    mark("aux Merkle");
-    ps.enqueue("aux root", commit(AUX, nullptr).data(), 5);
-    const std::vector<Xfe> quotient_weights = xfe_powers(ps.sample_scalars(1)[0], 0, TVM_NUM_QUOTIENT_WEIGHTS);
-
-    // 10: quotient, segments, randomization  (stark.rs:405-423).  The quotient codeword is not part of the proof.
-    mark("AIR quotients");
-    const u64 poly_len = std::max<u64>(p.quotient.length / 4, quotient_randomizer.size());
-    DeviceBuffer polys;
-    const TableGuard seg{c, quotient_segments(challenges, quotient_weights, zeta, polys, poly_len)};
-    // 12: quotient Merkle tree  (stark.rs:425-446)
-    mark("quotient Merkle");
-    ps.enqueue("quot root", commit(QUOT, seg.t).data(), 5);
-
     // 13: out-of-domain rows  (stark.rs:450-495)
     mark("out-of-domain rows");
     const Xfe alpha = ps.sample_scalars(1)[0];
     const Xfe alpha_next = xfe_scale(alpha, p.trace.generator);
     const std::vector<u64> ood_main = out_of_domain_rows(main, {alpha, alpha_next});
     const std::vector<u64> ood_aux = out_of_domain_rows(aux, {alpha, alpha_next});
-    const Xfe a4 = xfe_powers(alpha, 4, 1)[0];
+    a4 = xfe_powers(alpha, 4, 1)[0];
     const Xfe za4 = xfe_powers(xfe_scale(alpha, zeta), 4, 1)[0];
     Xfe seg_ood[5][2];
     {
@@ -711,7 +679,7 @@ ProofStream ProofSteps::prove() {
     wp[4] = Xfe{{0, 0, 0}};
     wr[0] = Xfe{{0, 0, 0}};
     DeviceBuffer cw_p, cw_r;   // values of the P and R polynomials on the short domain (stark.rs:520-540)
-    segment_combinations(seg.t, polys, poly_len, short_rank, &wp[0], &wr[0], cw_p, cw_r);
+    segment_combinations(segments, polys, poly_len, short_rank, &wp[0], &wr[0], cw_p, cw_r);
     Xfe ma_values[2];
     {
         const Xfe pts[2] = {alpha, alpha_next};
@@ -733,6 +701,93 @@ ProofStream ProofSteps::prove() {
     cw_p.reset();
     cw_r.reset();
     comb.reset();
+    return combination;
+}
+
+static std::atomic<uint64_t> g_device_middle_proofs{0};   // tvmh_device_middle_proofs
+// TVMH_OPTION_DEVICE_MIDDLE: the quotient root into the sponge and steps 13-16 in one call, the sponge on the device
+// (tvm_out_of_domain_to_deep: one stream synchronisation instead of five) -- then the root and the six out-of-domain items are enqueued
+// from the block that came back and both samplings are replayed on this host's sponge, which must arrive at the same alpha, the same
+// three weights and the same state.  false: the call does not apply (no whole tables and whole quotient tree here: the sharded and
+// coset-wise provers) and nothing was enqueued or committed.
+bool ProofSteps::device_middle(const tvm_table* segments, const DeviceBuffer& polys, u64 poly_len, const ArithmeticDomain& short_dom, u64 zeta, Xfe& a4,
+                               DeviceBuffer& combination) {
+    const u64* tree = commit_whole_quotient_tree(segments);
+    if (!tree) return false;
+    mark("out-of-domain rows to DEEP");
+    const u64 n_main = main.n_cols(), n_aux = aux.n_cols();
+    std::vector<u64> block(TVM_MIDDLE_BLOCK_WORDS(n_main, n_aux));
+    combination = DeviceBuffer(c, short_dom.length * 3);
+    c.check(tvm_out_of_domain_to_deep(c.raw(), main.trace(), n_main, main.randomizers(), aux.trace(), n_aux, aux.randomizers(), p.trace.length, p.h,
+                                      p.trace.c(), polys.ptr(), poly_len, segments, tree, short_dom.c(), zeta, ps.sponge_state(), combination.ptr(),
+                                      block.data(), block.size()), "tvm_out_of_domain_to_deep");
+    const u64 *b = block.data(), *points = b + TVM_MIDDLE_POINTS, *rows_main = b + TVM_MIDDLE_MAIN_ROWS, *rows_aux = b + TVM_MIDDLE_AUX_ROWS(n_main),
+              *seg = b + TVM_MIDDLE_SEGMENTS(n_main, n_aux);
+    auto agree = [](bool same, const char* what) {
+        if (!same) throw Error(TVM_ERR_DEVICE, std::string("the device's Fiat-Shamir sponge and the host's disagree on ") + what);
+    };
+    ps.enqueue("quot root", b + TVM_MIDDLE_ROOT, 5);
+    const Xfe alpha = ps.sample_scalars(1)[0];
+    agree(std::memcmp(alpha.c, points, 3 * sizeof(u64)) == 0, "the out-of-domain point");
+    ps.enqueue("ood main", rows_main, n_main * 3);
+    ps.enqueue("ood aux", rows_aux, n_aux * 3);
+    ps.enqueue("ood main next", rows_main + n_main * 3, n_main * 3);
+    ps.enqueue("ood aux next", rows_aux + n_aux * 3, n_aux * 3);
+    u64 quot_p[12], quot_r[12];   // segments 0..3 at alpha^4, 1..4 at (zeta alpha)^4, out of [5][2][3]
+    for (int k = 0; k < 4; k++) {
+        std::memcpy(quot_p + 3 * k, seg + 3 * (2 * k), 3 * sizeof(u64));
+        std::memcpy(quot_r + 3 * k, seg + 3 * (2 * (k + 1) + 1), 3 * sizeof(u64));
+    }
+    ps.enqueue("ood quot p", quot_p, 12);
+    ps.enqueue("ood quot r", quot_r, 12);
+    const std::vector<Xfe> w3 = ps.sample_scalars(3);
+    agree(std::memcmp(w3[0].c, b + TVM_MIDDLE_WEIGHTS(n_main, n_aux), 9 * sizeof(u64)) == 0, "the combination weights");
+    agree(std::memcmp(ps.sponge_state(), b + TVM_MIDDLE_STATE(n_main, n_aux), 16 * sizeof(u64)) == 0, "the state after the combination weights");
+    std::memcpy(a4.c, points + 6, 3 * sizeof(u64));   // step 18 checks it against the revealed points
+    g_device_middle_proofs++;
+    return true;
+}
+
+ProofStream ProofSteps::prove() {
+    ps.alter_fiat_shamir_state_with(claim.encode());  // stark.rs:336-339
+    {
+        const u64 log2_padded_height = to_mont(bit_length(p.padded_height) - 1);  // stark.rs:354
+        ps.enqueue("log2 padded height", &log2_padded_height, 1);
+    }
+    const u64 L = p.ldt.length;
+    const ArithmeticDomain short_dom = p.ldt.length <= p.quotient.length ? p.ldt : p.quotient;
+    const ArithmeticDomain ldt_rank = local(p.ldt), short_rank = local(short_dom);   // (one rank: the domains themselves)
+    const u64 zeta = to_mont(3);  // Stark::ZETA, stark.rs:1801
+
+    // 4-6: main table LDE, Merkle tree, challenges  (stark.rs:367-377)
+    mark("main LDE");
+    extend_master_table(MAIN);
+    mark("main Merkle");
+    ps.enqueue("main root", commit(MAIN, nullptr).data(), 5);
+    const std::vector<Xfe> challenges = derive_challenges(ps.sample_scalars(NUM_SAMPLED_CHALLENGES), claim);
+    mark("extend");
+    if (extend) extend(challenges);  // MasterMainTable::extend (stark.rs:379-381); over ranks: replicated
+
+    // 8-9: aux table (its `extend` is host work in the reference; the trace is already resident)
+    mark("aux LDE");
+    extend_master_table(AUX);
+    mark("aux Merkle");
+    ps.enqueue("aux root", commit(AUX, nullptr).data(), 5);
+    const std::vector<Xfe> quotient_weights = xfe_powers(ps.sample_scalars(1)[0], 0, TVM_NUM_QUOTIENT_WEIGHTS);
+
+    // 10: quotient, segments, randomization  (stark.rs:405-423).  The quotient codeword is not part of the proof.
+    mark("AIR quotients");
+    const u64 poly_len = std::max<u64>(p.quotient.length / 4, quotient_randomizer.size());
+    DeviceBuffer polys;
+    const TableGuard seg{c, quotient_segments(challenges, quotient_weights, zeta, polys, poly_len)};
+    // 12: quotient Merkle tree  (stark.rs:425-446); 13-16: out-of-domain rows, linear combinations, DEEP  (stark.rs:450-639)
+    mark("quotient Merkle");
+    Xfe a4;
+    DeviceBuffer combination;
+    if (!(tvmh_get_option(TVMH_OPTION_DEVICE_MIDDLE) && device_middle(seg.t, polys, poly_len, short_rank, zeta, a4, combination))) {
+        ps.enqueue("quot root", commit(QUOT, seg.t).data(), 5);
+        combination = host_middle(seg.t, polys, poly_len, short_rank, zeta, a4);
+    }
     if (short_dom.length != L) {  // stark.rs:629-639: the quotient domain was the short one -- extend to the LDT domain
         const DeviceBuffer whole = gather_rows(std::move(combination), short_rank.length, 3, "combination codeword (short domain)");
         const DeviceBuffer coeffs = p.quotient.interpolate(c, whole.ptr(), 3);
@@ -802,10 +857,17 @@ struct WholeSteps : ProofSteps {
         return true;
     }
     Words commit(Which w, const tvm_table* segments) override {
+        build_tree(w, segments);
+        return merkle_root(c, nodes[w]);
+    }
+    const u64* commit_whole_quotient_tree(const tvm_table* segments) override {   // (the root stays on the device: no round trip)
+        build_tree(QUOT, segments);
+        return nodes[QUOT].ptr();
+    }
+    void build_tree(Which w, const tvm_table* segments) {
         if (w == QUOT) segment_table = segments;
         nodes[w] = DeviceBuffer(c, 10 * p.ldt.length);
         c.check(tvm_table_merkle_tree(c.raw(), w == QUOT ? segments : master(w).table(), p.ldt.length, nodes[w].ptr()), "tvm_table_merkle_tree");
-        return merkle_root(c, nodes[w]);
     }
     // Where the AIR arrives at the quotient's coefficients (valid-trace mode on a long trace) the segments are taken from them, and
     // only elsewhere (exact mode, short traces, other expansion factors) a codeword is made and interpolated.
@@ -1277,14 +1339,15 @@ std::vector<u64> prove_execution(const Context& c, const StarkParameters& p, con
 
 }  // namespace triton_vm
 
-static std::atomic<uint64_t> g_options[8] = {{0}, {0}, {0}, {0}, {0}, {0}, {0}, {0}};   // indexed by TVMH_OPTION_*
+static std::atomic<uint64_t> g_options[9] = {{0}, {0}, {0}, {0}, {0}, {0}, {0}, {0}, {0}};   // indexed by TVMH_OPTION_*
 extern "C" void tvmh_set_option(uint32_t option, uint64_t value) {
-    if (option >= 1 && option <= 7) g_options[option].store(value);
+    if (option >= 1 && option <= 8) g_options[option].store(value);
 }
-extern "C" uint64_t tvmh_get_option(uint32_t option) { return option >= 1 && option <= 7 ? g_options[option].load() : 0; }
+extern "C" uint64_t tvmh_get_option(uint32_t option) { return option >= 1 && option <= 8 ? g_options[option].load() : 0; }
 
 extern "C" uint64_t tvmh_device_tail_proofs(void) { return triton_vm::g_device_tail_proofs.load(); }
 extern "C" uint64_t tvmh_device_stir_proofs(void) { return triton_vm::g_device_stir_proofs.load(); }
+extern "C" uint64_t tvmh_device_middle_proofs(void) { return triton_vm::g_device_middle_proofs.load(); }
 
 extern "C" int32_t tvmh_prove(tvm_ctx* ctx, uint32_t log2_padded_height, uint64_t num_trace_randomizers,
                               uint64_t num_collinearity_checks, uint32_t log2_expansion, const uint64_t* d_main_trace,

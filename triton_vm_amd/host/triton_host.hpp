@@ -135,6 +135,8 @@ public:
     DeviceBuffer weighted_sum_of_columns(const Xfe* weights) const;       // :512-542 -> 2 * n_rows XFE coefficients
     int field_kind() const { return fk_; }
     u64 n_cols() const { return n_cols_; }
+    const u64* trace() const { return d_trace_; }              // [n_cols][n_rows] elements on the device, column-major
+    const u64* randomizers() const { return d_rnd_; }          // [n_cols][num_trace_randomizers] elements
     // the quotient / LDT domain this table is extended onto: a coset group of the real domains when the extended rows are
     // split over ranks or evaluated pass by pass (sharded_host.cpp); drops the cached extension
     void set_domains(ArithmeticDomain quotient, ArithmeticDomain ldt);
@@ -534,6 +536,16 @@ extern "C" uint64_t tvmh_device_tail_proofs(void);
 #define TVMH_OPTION_DEVICE_STIR 7
 // how many calls of Stir::prove in this process took that path so far (one it does not apply to is not counted)
 extern "C" uint64_t tvmh_device_stir_proofs(void);
+// TVMH_OPTION_DEVICE_MIDDLE != 0: a single-GPU proof (FRI or STIR) runs steps 12-16 of Prover::prove behind the quotient's Merkle tree -- the
+// root into the sponge, the out-of-domain point, rows and segment values, the three combination weights, the linear combinations and
+// DEEP -- in one call with the sponge on the device (tvm_out_of_domain_to_deep: one stream synchronisation instead of five, no host work
+// in between); the host enqueues the root and the six out-of-domain items from the block that comes back, replays both samplings on its
+// own sponge and throws TVM_ERR_DEVICE when the out-of-domain point, a weight or the state differs.  The same proof, word for word.
+// Default 0.  The sharded and coset-wise provers (no whole traces and whole quotient tree on one GPU) keep the host's path whatever the
+// value.  Works together with TVMH_OPTION_DEVICE_TAIL and TVMH_OPTION_DEVICE_STIR.
+#define TVMH_OPTION_DEVICE_MIDDLE 8
+// how many proofs of this process took that path so far (a proof it does not apply to is not counted)
+extern "C" uint64_t tvmh_device_middle_proofs(void);
 extern "C" void tvmh_set_option(uint32_t option, uint64_t value);
 extern "C" uint64_t tvmh_get_option(uint32_t option);
 

@@ -53,6 +53,8 @@ def load_host_library(backend_path=None, out=None):
     lib.tvmh_device_tail_proofs.argtypes = []
     lib.tvmh_device_stir_proofs.restype = C.c_uint64
     lib.tvmh_device_stir_proofs.argtypes = []
+    lib.tvmh_device_middle_proofs.restype = C.c_uint64
+    lib.tvmh_device_middle_proofs.argtypes = []
     lib.tvmh_local_comms_create.restype = C.c_int32
     lib.tvmh_local_comms_create.argtypes = [C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)]
     lib.tvmh_local_comms_destroy.restype = None
@@ -71,6 +73,7 @@ OPTION_COLUMN_SPLIT = 4   # k > 0: the sharded prover splits the inverse transfo
 OPTION_CHECK_TRACE = 5   # prove_execution checks the AIR on the trace first and proves a trace that fails in exact mode
 OPTION_DEVICE_TAIL = 6   # single-GPU FRI proofs: the query phase and the trace openings in one device round trip (proof_tail.py)
 OPTION_DEVICE_STIR = 7   # Stir::prove: all rounds in one call with the sponge on the device (stir_rounds.py)
+OPTION_DEVICE_MIDDLE = 8   # single-GPU proofs: the quotient root, the out-of-domain rows, the combinations and DEEP in one device round trip (proof_middle.py)
 
 
 class host_option:
