@@ -34,7 +34,9 @@
         }                                                                               \
     } while (0)
 
-// MODE 0: the whole round.  1: the power maps only.  2: the MDS layer only.  3: the lookup word only.
+// MODE 0: the whole round (the permutation whose state is read afterwards: its last round makes every word canonical).  1: the power maps
+// only.  2: the MDS layer only.  3: the lookup word only.  4: the whole round of the permutation BETWEEN two blocks of a row (no round
+// makes st[1..3] canonical: tip5_permute_mfma<false>, 37 of the 38 permutations of a main-table row).
 template <int MODE>
 __device__ __forceinline__ void round_parts(u64 (&st)[4], const Tip5MfmaOperands& m, int g, const unsigned char* lut, const int* ctab, int r) {
     if constexpr (MODE == 1) {
@@ -80,6 +82,7 @@ __global__ void __launch_bounds__(256, 6) k_rounds(u64* __restrict__ out, int n_
     for (int t = 0; t < 4; t++) st[t] = (u64)(blockIdx.x * 256 + tid) * 0x9E3779B97F4A7C15ull + t;
     for (int p = 0; p < n_perm; p++) {
         if constexpr (MODE == 0) tip5_permute_mfma(st, a, g, lut, ctab);
+        else if constexpr (MODE == 4) tip5_permute_mfma<false>(st, a, g, lut, ctab);
         else
             for (int r = 0; r < TIP5_ROUNDS; r++) round_parts<MODE>(st, a, g, lut, ctab, r);
     }
@@ -125,9 +128,10 @@ int main(int argc, char** argv) {
     // (1), (2): 24 wavefronts per CU resident (six workgroups of four), 16 waves of workgroups per CU, 32 permutations each
     const int workgroups = n_cus * 6 * 16, n_perm = 32;
     const Timing whole = run<0>(workgroups, n_perm, n_simds), x7 = run<1>(workgroups, n_perm, n_simds), mds = run<2>(workgroups, n_perm, n_simds),
-                 look = run<3>(workgroups, n_perm, n_simds);
+                 look = run<3>(workgroups, n_perm, n_simds), between = run<4>(workgroups, n_perm, n_simds);
     std::printf("registers-only, %d workgroups x 256 work-items x %d permutations, best of 5:\n", workgroups, n_perm);
     std::printf("  whole round (tip5_permute_mfma)        %8.3f ms   %7.1f SIMD-ns per wavefront-round\n", whole.ms, whole.simd_ns_per_wave_round);
+    std::printf("  whole round, between two blocks of a row %6.3f ms   %7.1f\n", between.ms, between.simd_ns_per_wave_round);
     std::printf("  three x^7 per lane                     %8.3f ms   %7.1f\n", x7.ms, x7.simd_ns_per_wave_round);
     std::printf("  MDS layer (prep + 12 MFMA + recombine) %8.3f ms   %7.1f\n", mds.ms, mds.simd_ns_per_wave_round);
     std::printf("  split-and-lookup word                  %8.3f ms   %7.1f\n", look.ms, look.simd_ns_per_wave_round);

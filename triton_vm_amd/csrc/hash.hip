@@ -38,7 +38,8 @@ __global__ void __launch_bounds__(TVM_HASH_BLOCK, 6) k_hash_rows_mfma(const u64*
     const int lane = tid & 63, n = lane & 15, g = lane >> 4;
     // the view's rows in the order that walks storage contiguously (context.h: TabView); digest r goes to the row's index
     // in the domain
-    const u64 t = ((u64)blockIdx.x * (TVM_HASH_BLOCK / 64) + (tid >> 6)) * 16 + n;
+    const u64 t0 = ((u64)blockIdx.x * (TVM_HASH_BLOCK / 64) + tvm_uniform(tid >> 6)) * 16;   // (scalar)
+    const u64 t = t0 + n;
     const bool live = t < view.n_out;  // every lane of a wavefront takes part in the matrix instructions
     u64 row, r;
     view.locate(live ? t : view.n_out - 1, row, r);
@@ -56,7 +57,7 @@ __global__ void __launch_bounds__(TVM_HASH_BLOCK, 6) k_hash_rows_mfma(const u64*
         st[1] = TVM_LOAD_STREAM(p + 4 * TVM_RB);
         if (g < 2) st[2] = TVM_LOAD_STREAM(p + 8 * TVM_RB);
         p += TIP5_RATE * TVM_RB;
-        tip5_permute_mfma(st, a, g, lut, ctab, true);   // (a block always follows: the one with the padding)
+        tip5_permute_mfma<false>(st, a, g, lut, ctab, true);   // (a block always follows, the one with the padding: nobody reads this state as words)
     }
 #pragma unroll
     for (int t3 = 0; t3 < 3; t3++) {
@@ -77,6 +78,14 @@ __global__ void __launch_bounds__(TVM_HASH_BLOCK, 6) k_hash_rows_mfma(const u64*
     }
 #endif
     if (live) {
+        // the digest's index once more, from scalars and the lane's number as the hardware counts it: kept in registers across the
+        // permutations it was the kernel's one spill (profiles/tip5_diet_kernel_static_properties.txt)
+#ifdef TVM_EMU
+        const int n_again = n;
+#else
+        const int n_again = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)) & 15;
+#endif
+        view.locate(t0 + n_again, row, r);
         digests[r * 5 + g] = st[0];
         if (g == 0) digests[r * 5 + 4] = st[1];
     }

@@ -176,8 +176,8 @@ TVM_D u64 tip5_permute_lanes(u64 x, int pos, int lane, const unsigned char* lut)
 //   128 * sum(digits present at that position), a bias 2^21 that keeps every T_c positive, and byte c of the (adjusted)
 //   round constant.
 //
-// The remaining VALU work per word is the recombination of ten 22-bit sums into one field element (17 instructions:
-// tip5_mfma_recombine), against ~62 for the all-VALU form.
+// The remaining VALU work per word is the recombination of ten 22-bit sums into one field element (tip5_mfma_recombine: five shift-adds,
+// three multiply-adds and a carry tail of four or six instructions), against ~62 for the all-VALU form.
 #ifdef TVM_EMU
 struct tvm_v4i {
     int v[4];
@@ -280,29 +280,59 @@ TVM_D Tip5MfmaOperands tip5_mfma_matrix_operands(int lane) {
     return o;
 }
 
-// Ten 22-bit sums D_c per word -> sum_c 2^(8c) D_c mod p, canonical, for the four words of a lane.
-//   P0 = D_0 + 2^8 D_1 + 2^16 D_2 + 2^24 D_3 (< 2^47) and P1 likewise from D_4..D_7 (weight 2^32): chains of v_mad_u64_u32,
-//   the first with a zero addend, so that no 32-bit value has to be widened into an aligned register pair;
-//   2^64 = EPS (mod p):  value = P0 + 2^32 lo(P1) + h * EPS,  h = hi(P1) + D_8 + 2^8 D_9 (< 2^31);
-//   t = h * EPS + P0 < 2^63;  s = t + 2^32 lo(P1) (carry c): the value is s + 2^64 c, and it is canonical after ONE
-//   subtraction of p (= addition of EPS modulo 2^64) exactly when c is set (then s < t < 2^63) or s >= p, i.e. when
-//   z = s + EPS carries (c2):  result = (c | c2) ? z : s  -- the shape of bfe_add's tail.
-// The tail of the four words is one instruction stream, chain by chain (carries in VCC and seven SGPR pairs), so that
-// every carry consumer has at least two instructions between it and its producer (field.h: TVM_VCC_WAIT).
+// Ten 22-bit sums D_c per word -> sum_c 2^(8c) D_c mod p, for the four words of a lane.
+//   Every D_c is positive and below 2^22: with the lowering of the bytes undone by the table's correction it is the bias 2^21
+//   (TIP5_MFMA_BIAS_LOG) + at most 48 products digit * byte (|digit| <= 128, byte <= 255: below 2^20.6 in magnitude together) + a byte
+//   of the round constant -- so the pairs E_k = D_2k + 2^8 D_(2k+1) (< 2^31) fit a 32-bit register and are one v_lshl_add_u32 each
+//   (TVM_TIP5_SHIFT_ADD; rates: profiles/tip5_diet_valu_rates.txt);
+//   P0 = E_0 + 2^16 E_1 = D_0 + 2^8 D_1 + 2^16 D_2 + 2^24 D_3 (< 2^47) and P1 = E_2 + 2^16 E_3 likewise from D_4..D_7 (weight 2^32): one
+//   v_mad_u64_u32 each, by a 2^16 the compiler cannot see through (it would widen every term into a register pair otherwise);
+//   2^64 = EPS (mod p):  value = P0 + 2^32 lo(P1) + h * EPS,  h = hi(P1) + E_4 = hi(P1) + D_8 + 2^8 D_9 (< 2^31 + 2^16);
+//   t = h * EPS + P0 < 2^63;  s = t + 2^32 lo(P1) (carry k): the value is s + 2^64 k.
+//   CANONICAL tail (six instructions a word): the value is canonical after ONE subtraction of p (= addition of EPS modulo 2^64) exactly
+//   when k is set (then s < t < 2^63) or s >= p, i.e. when z = s + EPS carries (c2):  result = (k | c2) ? z : s  -- the shape of
+//   bfe_add's tail.
+//   FOLDED tail (four instructions a word: the words nobody reads as words): result = k ? s + EPS : s, some 64-bit representative of
+//   the residue.  A second wrap is impossible: k set means s < t < 2^63, so s + EPS < 2^64.
+// Who may be handed a folded word.  st[0] is ALWAYS canonical: the S-box table is indexed by the bytes of the canonical Montgomery
+// word.  st[1..3] go to tip5_pow7 in the next round, and bfe_mul / bfe_sqr are residue-correct on ANY 64-bit inputs: the partial
+// products of two 64-bit words assemble without overflow (field.h: u <= (2^32-1)^2 + 2^32 - 1, w likewise with the carry beside v1), and
+// bfe_montyred subtracts b <= p - 1 (a function of the low half alone) from the high half hi < 2^64, adding p back on a borrow -- a
+// 64-bit representative of x 2^-64 for every hi, canonical or not.  The chain's output goes to the matrix cores as bytes, and the MDS
+// layer is linear over the integers (every D_c is bounded by the BYTES, whatever word they spell), so the next recombination reduces
+// the same residue.  Canonical words are owed only where the state is read as words after the round: the digest of a sponge's last
+// permutation and the Merkle parents (ALL_CANONICAL in the last round of tip5_permute_mfma<true>).
+// The tail of the four words is one instruction stream, chain by chain (carries in VCC and SGPR pairs), so that every carry consumer
+// has at least two instructions between it and its producer (field.h: TVM_VCC_WAIT).  Which tail is a COMPILE-TIME choice: a
+// run-time branch between two tails spilled a matrix operand per round (round 6, below).
 // `lean` (uniform over the wavefront): the words v = 0, 1 are NOT owed -- the caller overwrites them (tip5_permute_mfma with rate_is_overwritten) --
-// so their multiply-add chains are skipped (18 instructions); the carry tail below stays the one four-chain block and turns
-// whatever it is given for them into values nobody reads.
+// so their multiply-add chains are skipped; the carry tail below stays the one four-chain block and turns whatever it is given for
+// them into values nobody reads.  st[2], st[3] (capacity words for the lanes g >= 2, kept across the absorb) are folded like any other.
 #ifndef TVM_TIP5_LEAN_ROUND
 #define TVM_TIP5_LEAN_ROUND 1   // 0: the last round recombines the rate words all the same (A/B: profiles/r06_n_*, 43.0-43.3 against 43.4-43.6 ms)
 #endif
+#ifndef TVM_TIP5_SHIFT_ADD
+#define TVM_TIP5_SHIFT_ADD 1    // 0: P0, P1 as chains of three v_mad_u64_u32 by 2^8, 2^16, 2^24 (A/B: profiles/tip5_diet_bench_ab.txt)
+#endif
+#ifndef TVM_TIP5_FOLDED_WORDS
+#define TVM_TIP5_FOLDED_WORDS 1 // 0: every word of every round canonical (A/B: profiles/tip5_diet_bench_ab.txt)
+#endif
+template <bool ALL_CANONICAL = true>
 TVM_D void tip5_mfma_recombine(const tvm_v4i (&d)[TIP5_MFMA_POSITIONS], u64 (&st)[4], bool lean = false) {
+    constexpr bool FOLDED = TVM_TIP5_FOLDED_WORDS && !ALL_CANONICAL;
     u64 t[4];
     u32 pl[4];
-    // the shifts as multiplications by values the compiler cannot see through (it would widen every term into a register
-    // pair and use 64-bit shifts and additions instead of one v_mad_u64_u32 per term)
+    // the shifts as multiplications by values the compiler cannot see through
+#if TVM_TIP5_SHIFT_ADD
+    u32 w16 = 1u << 16;
+#ifdef TVM_FIELD_ASM
+    asm("" : "+s"(w16));
+#endif
+#else
     u32 w8 = 1u << 8, w16 = 1u << 16, w24 = 1u << 24;
 #ifdef TVM_FIELD_ASM
     asm("" : "+s"(w8), "+s"(w16), "+s"(w24));
+#endif
 #endif
 #pragma unroll
     for (int v = 0; v < 4; v++) {
@@ -311,6 +341,14 @@ TVM_D void tip5_mfma_recombine(const tvm_v4i (&d)[TIP5_MFMA_POSITIONS], u64 (&st
             pl[v] = (u32)d[4][v];
             continue;
         }
+#if TVM_TIP5_SHIFT_ADD
+        const u32 e0 = (u32)d[0][v] + ((u32)d[1][v] << 8), e1 = (u32)d[2][v] + ((u32)d[3][v] << 8);
+        const u32 e2 = (u32)d[4][v] + ((u32)d[5][v] << 8), e3 = (u32)d[6][v] + ((u32)d[7][v] << 8);
+        const u32 e4 = (u32)d[8][v] + ((u32)d[9][v] << 8);
+        const u64 p0 = (u64)e1 * w16 + e0;
+        const u64 p1 = (u64)e3 * w16 + e2;
+        const u32 h = (u32)(p1 >> 32) + e4;
+#else
         u64 p0 = (u64)(u32)d[1][v] * w8;
         p0 += (u64)(u32)d[2][v] * w16;
         p0 += (u64)(u32)d[3][v] * w24;
@@ -320,37 +358,65 @@ TVM_D void tip5_mfma_recombine(const tvm_v4i (&d)[TIP5_MFMA_POSITIONS], u64 (&st
         p1 += (u64)(u32)d[7][v] * w24;
         p1 += (u32)d[4][v];
         const u32 h = (u32)(p1 >> 32) + (u32)d[8][v] + ((u32)d[9][v] << 8);
+#endif
         t[v] = (u64)h * 0xFFFFFFFFu + p0;
         pl[v] = (u32)p1;
     }
 #ifdef TVM_FIELD_ASM
     u32 sh0, sh1, sh2, sh3, zl0, zl1, zl2, zl3, zh0, zh1, zh2, zh3;
-    u64 k0, k1, k2, k3, c1, c2, c3;
+    u64 k0, k1, k2, k3;
 #define TIP5_R1(i, K) "v_add_co_u32_e64 %[sh" #i "], " K ", %[th" #i "], %[pl" #i "]\n\t"
 #define TIP5_R2(i, C) "v_add_co_u32_e64 %[zl" #i "], " C ", -1, %[tl" #i "]\n\t"
 #define TIP5_R3(i, C) "v_addc_co_u32_e64 %[zh" #i "], " C ", 0, %[sh" #i "], " C "\n\t"
 #define TIP5_R4(i, C, K) "s_or_b64 " C ", " C ", " K "\n\t"
 #define TIP5_R5(i, C) "v_cndmask_b32_e64 %[zl" #i "], %[tl" #i "], %[zl" #i "], " C "\n\t"
 #define TIP5_R6(i, C) "v_cndmask_b32_e64 %[sh" #i "], %[sh" #i "], %[zh" #i "], " C "\n\t"
-    asm(TIP5_R1(0, "%[k0]") TIP5_R1(1, "%[k1]") TIP5_R1(2, "%[k2]") TIP5_R1(3, "%[k3]")
-        TIP5_R2(0, "vcc") TIP5_R2(1, "%[c1]") TIP5_R2(2, "%[c2]") TIP5_R2(3, "%[c3]")
-        TIP5_R3(0, "vcc") TIP5_R3(1, "%[c1]") TIP5_R3(2, "%[c2]") TIP5_R3(3, "%[c3]")
-        TIP5_R4(0, "vcc", "%[k0]") TIP5_R4(1, "%[c1]", "%[k1]") TIP5_R4(2, "%[c2]", "%[k2]") TIP5_R4(3, "%[c3]", "%[k3]")
-        TIP5_R5(0, "vcc") TIP5_R5(1, "%[c1]") TIP5_R5(2, "%[c2]") TIP5_R5(3, "%[c3]")
-        TIP5_R6(0, "vcc") TIP5_R6(1, "%[c1]") TIP5_R6(2, "%[c2]") TIP5_R6(3, "%[c3]")
-        : [sh0] "=&v"(sh0), [sh1] "=&v"(sh1), [sh2] "=&v"(sh2), [sh3] "=&v"(sh3), [zl0] "=&v"(zl0), [zl1] "=&v"(zl1),
-          [zl2] "=&v"(zl2), [zl3] "=&v"(zl3), [zh0] "=&v"(zh0), [zh1] "=&v"(zh1), [zh2] "=&v"(zh2), [zh3] "=&v"(zh3),
-          [k0] "=&s"(k0), [k1] "=&s"(k1), [k2] "=&s"(k2), [k3] "=&s"(k3), [c1] "=&s"(c1), [c2] "=&s"(c2), [c3] "=&s"(c3)
-        : [tl0] "v"((u32)t[0]), [th0] "v"((u32)(t[0] >> 32)), [pl0] "v"(pl[0]), [tl1] "v"((u32)t[1]), [th1] "v"((u32)(t[1] >> 32)),
-          [pl1] "v"(pl[1]), [tl2] "v"((u32)t[2]), [th2] "v"((u32)(t[2] >> 32)), [pl2] "v"(pl[2]), [tl3] "v"((u32)t[3]),
-          [th3] "v"((u32)(t[3] >> 32)), [pl3] "v"(pl[3])
-        : "vcc", "scc");
+// the folded tail: EPS where the carry K is set (zh is the scratch register), added to the pair (tl, sh); K is free after F2 and takes the low half's carry
+#define TIP5_F2(i, K) "v_cndmask_b32_e64 %[zh" #i "], 0, -1, " K "\n\t"
+#define TIP5_F3(i, K) "v_add_co_u32_e64 %[zl" #i "], " K ", %[tl" #i "], %[zh" #i "]\n\t"
+#define TIP5_F4(i, K) "v_addc_co_u32_e64 %[sh" #i "], " K ", 0, %[sh" #i "], " K "\n\t"
+#define TIP5_TAIL_OUT                                                                                                          \
+    [sh0] "=&v"(sh0), [sh1] "=&v"(sh1), [sh2] "=&v"(sh2), [sh3] "=&v"(sh3), [zl0] "=&v"(zl0), [zl1] "=&v"(zl1), [zl2] "=&v"(zl2), \
+        [zl3] "=&v"(zl3), [zh0] "=&v"(zh0), [zh1] "=&v"(zh1), [zh2] "=&v"(zh2), [zh3] "=&v"(zh3), [k0] "=&s"(k0), [k1] "=&s"(k1),  \
+        [k2] "=&s"(k2), [k3] "=&s"(k3)
+#define TIP5_TAIL_IN                                                                                                            \
+    [tl0] "v"((u32)t[0]), [th0] "v"((u32)(t[0] >> 32)), [pl0] "v"(pl[0]), [tl1] "v"((u32)t[1]), [th1] "v"((u32)(t[1] >> 32)),       \
+        [pl1] "v"(pl[1]), [tl2] "v"((u32)t[2]), [th2] "v"((u32)(t[2] >> 32)), [pl2] "v"(pl[2]), [tl3] "v"((u32)t[3]),               \
+        [th3] "v"((u32)(t[3] >> 32)), [pl3] "v"(pl[3])
+    if constexpr (FOLDED) {
+        // word 0 canonical (chain in VCC), words 1..3 folded (chains in their own carry pairs): every reader of a carry is at least
+        // three instructions behind its writer
+        asm(TIP5_R1(0, "%[k0]") TIP5_R1(1, "%[k1]") TIP5_R1(2, "%[k2]") TIP5_R1(3, "%[k3]")
+            TIP5_R2(0, "vcc") TIP5_F2(1, "%[k1]") TIP5_F2(2, "%[k2]") TIP5_F2(3, "%[k3]")
+            TIP5_R3(0, "vcc") TIP5_F3(1, "%[k1]") TIP5_F3(2, "%[k2]") TIP5_F3(3, "%[k3]")
+            TIP5_R4(0, "vcc", "%[k0]") TIP5_F4(1, "%[k1]") TIP5_F4(2, "%[k2]") TIP5_F4(3, "%[k3]")
+            TIP5_R5(0, "vcc") TIP5_R6(0, "vcc")
+            : TIP5_TAIL_OUT
+            : TIP5_TAIL_IN
+            : "vcc", "scc");
+    } else {
+        u64 c1, c2, c3;
+        asm(TIP5_R1(0, "%[k0]") TIP5_R1(1, "%[k1]") TIP5_R1(2, "%[k2]") TIP5_R1(3, "%[k3]")
+            TIP5_R2(0, "vcc") TIP5_R2(1, "%[c1]") TIP5_R2(2, "%[c2]") TIP5_R2(3, "%[c3]")
+            TIP5_R3(0, "vcc") TIP5_R3(1, "%[c1]") TIP5_R3(2, "%[c2]") TIP5_R3(3, "%[c3]")
+            TIP5_R4(0, "vcc", "%[k0]") TIP5_R4(1, "%[c1]", "%[k1]") TIP5_R4(2, "%[c2]", "%[k2]") TIP5_R4(3, "%[c3]", "%[k3]")
+            TIP5_R5(0, "vcc") TIP5_R5(1, "%[c1]") TIP5_R5(2, "%[c2]") TIP5_R5(3, "%[c3]")
+            TIP5_R6(0, "vcc") TIP5_R6(1, "%[c1]") TIP5_R6(2, "%[c2]") TIP5_R6(3, "%[c3]")
+            : TIP5_TAIL_OUT, [c1] "=&s"(c1), [c2] "=&s"(c2), [c3] "=&s"(c3)
+            : TIP5_TAIL_IN
+            : "vcc", "scc");
+    }
 #undef TIP5_R1
 #undef TIP5_R2
 #undef TIP5_R3
 #undef TIP5_R4
 #undef TIP5_R5
 #undef TIP5_R6
+#undef TIP5_F2
+#undef TIP5_F3
+#undef TIP5_F4
+#undef TIP5_TAIL_OUT
+#undef TIP5_TAIL_IN
     st[0] = ((u64)sh0 << 32) | zl0;
     st[1] = ((u64)sh1 << 32) | zl1;
     st[2] = ((u64)sh2 << 32) | zl2;
@@ -359,7 +425,8 @@ TVM_D void tip5_mfma_recombine(const tvm_v4i (&d)[TIP5_MFMA_POSITIONS], u64 (&st
 #pragma unroll
     for (int v = 0; v < 4; v++) {
         const u64 s = t[v] + ((u64)pl[v] << 32), z = s + TVM_EPS;
-        st[v] = ((s < t[v]) | (z < s)) ? z : s;
+        if (FOLDED && v > 0) st[v] = s < t[v] ? z : s;
+        else st[v] = ((s < t[v]) | (z < s)) ? z : s;
     }
 #endif
 }
@@ -377,37 +444,51 @@ TVM_D void tip5_mfma_recombine(const tvm_v4i (&d)[TIP5_MFMA_POSITIONS], u64 (&st
 //    What the 6.5-7 % are, by count: the absorb's own instructions 1.7 %, workgroup set-up and relaunch ~1.2 %, the launch's last
 //    wave of workgroups (85.3 rounds of them: one in 86) ~1.2 %; the rest (~2.5 %) moves with the memory traffic, not with the code.
 //
-// st[t] = word g + 4t of the state of permutation n; every lane of the wavefront must take part.  `lut` is the S-box table
-// LOWERED by 128 (tip5_stage_lut_lowered): the looked-up word goes to the matrix cores only, where bytes travel that way.
+// One round.  st[t] = word g + 4t of the state of permutation n; `lut` is the S-box table LOWERED by 128.  ALL_CANONICAL: the state is
+// read as words after this round (tip5_mfma_recombine); otherwise st[1..3] come back as folded representatives.
+template <bool ALL_CANONICAL>
+TVM_D void tip5_round_mfma(u64 (&st)[4], const Tip5MfmaOperands& m, int g, const unsigned char* lut, const int* ctab, int r, bool lean) {
+    // accumulator inputs first: their LDS latency hides behind the S-box layer
+    tvm_v4i d[TIP5_MFMA_POSITIONS];
+#pragma unroll
+    for (int c = 0; c < TIP5_MFMA_POSITIONS; c++) {
+        const int* cp = ctab + ((r * TIP5_MFMA_POSITIONS + c) * 4 + g) * 4;
+#pragma unroll
+        for (int v = 0; v < 4; v++) d[c][v] = cp[v];
+    }
+    st[0] = tip5_sbox_lookup(st[0], lut);
+#pragma unroll
+    for (int t = 1; t < 4; t++) st[t] = tip5_pow7(st[t]);
+    const u32 pad = 0x80808080u;  // bytes travel lowered by 128
+    tvm_v4i lo, hi;
+    lo[0] = (int)(u32)st[0];
+    hi[0] = (int)(u32)(st[0] >> 32);
+#pragma unroll
+    for (int t = 1; t < 4; t++) {
+        lo[t] = (int)((u32)st[t] ^ pad);
+        hi[t] = (int)((u32)(st[t] >> 32) ^ pad);
+    }
+#pragma unroll
+    for (int s = 0; s < TIP5_MFMA_SHIFTS; s++) d[s] = TVM_MFMA_I8(m.a[s], lo, d[s]);
+#pragma unroll
+    for (int s = 0; s < TIP5_MFMA_SHIFTS; s++) d[s + 4] = TVM_MFMA_I8(m.a[s], hi, d[s + 4]);
+    tip5_mfma_recombine<ALL_CANONICAL>(d, st, lean);
+}
+
+// st[t] = word g + 4t of the state of permutation n (st[0] canonical on entry; st[1..3] any representative); every lane of the wavefront
+// must take part.  `lut` is the
+// S-box table LOWERED by 128 (tip5_stage_lut_lowered): the looked-up word goes to the matrix cores only, where bytes travel that way.
+// CANONICAL_OUT (compile time): the caller reads the state as words afterwards -- a digest, a Merkle parent, a squeeze, an absorb in
+// addition mode -- so the LAST round makes every word canonical; the rounds before it never do (only their st[0], for the table
+// lookup).  Without it (a sponge in overwrite mode between two blocks of a row) the state comes back with st[0] canonical and
+// st[1..3] as folded representatives, good for another tip5_permute_mfma and nothing else.
 // `rate_is_overwritten` (uniform): the caller absorbs the next block in overwrite mode right after this permutation, i.e. replaces the
 // words 0 .. 9 -- st[0], st[1] of every lane and st[2] of the lanes g < 2 -- so the last round need not produce st[0], st[1].
+template <bool CANONICAL_OUT = true>
 TVM_D void tip5_permute_mfma(u64 (&st)[4], const Tip5MfmaOperands& m, int g, const unsigned char* lut, const int* ctab,
                              bool rate_is_overwritten = false) {
-    for (int r = 0; r < TIP5_ROUNDS; r++) {
-        // accumulator inputs first: their LDS latency hides behind the S-box layer
-        tvm_v4i d[TIP5_MFMA_POSITIONS];
-#pragma unroll
-        for (int c = 0; c < TIP5_MFMA_POSITIONS; c++) {
-            const int* cp = ctab + ((r * TIP5_MFMA_POSITIONS + c) * 4 + g) * 4;
-#pragma unroll
-            for (int v = 0; v < 4; v++) d[c][v] = cp[v];
-        }
-        st[0] = tip5_sbox_lookup(st[0], lut);
-#pragma unroll
-        for (int t = 1; t < 4; t++) st[t] = tip5_pow7(st[t]);
-        const u32 pad = 0x80808080u;  // bytes travel lowered by 128
-        tvm_v4i lo, hi;
-        lo[0] = (int)(u32)st[0];
-        hi[0] = (int)(u32)(st[0] >> 32);
-#pragma unroll
-        for (int t = 1; t < 4; t++) {
-            lo[t] = (int)((u32)st[t] ^ pad);
-            hi[t] = (int)((u32)(st[t] >> 32) ^ pad);
-        }
-#pragma unroll
-        for (int s = 0; s < TIP5_MFMA_SHIFTS; s++) d[s] = TVM_MFMA_I8(m.a[s], lo, d[s]);
-#pragma unroll
-        for (int s = 0; s < TIP5_MFMA_SHIFTS; s++) d[s + 4] = TVM_MFMA_I8(m.a[s], hi, d[s + 4]);
-        tip5_mfma_recombine(d, st, TVM_TIP5_LEAN_ROUND && rate_is_overwritten && r + 1 == TIP5_ROUNDS);
-    }
+    const bool lean = TVM_TIP5_LEAN_ROUND && rate_is_overwritten;
+    constexpr int folded_rounds = CANONICAL_OUT ? TIP5_ROUNDS - 1 : TIP5_ROUNDS;
+    for (int r = 0; r < folded_rounds; r++) tip5_round_mfma<false>(st, m, g, lut, ctab, r, lean && r + 1 == TIP5_ROUNDS);
+    if constexpr (CANONICAL_OUT) tip5_round_mfma<true>(st, m, g, lut, ctab, TIP5_ROUNDS - 1, lean);
 }
