@@ -85,6 +85,13 @@ int32_t tvm_ctx_trim(tvm_ctx* ctx);
  * at 2048 points runs k_lde_pass3_rows instead of k_lde_pass3_halves.  1024-point axes keep the row kernels of the first and last
  * pass, and axes of at most 128 or of 4096 points run the same kernels with either value (csrc/lde_plan.h decides all of this). */
 #define TVM_OPTION_LDE_PASS2_TILES 4
+/* TVM_OPTION_LDE_PASS1_WORKGROUPS: workgroups per launch of the first pass's row kernels on 256-, 512- and 1024-point axes
+ * (k_lde_pass1_rows<8 | 9 | 10, 16>), at most one per (column, tile) item of the chunk.  With fewer workgroups than items each walks
+ * several tiles with the next tile's input in flight under the current one's butterflies.  0 (default) and any value at or above the
+ * item count: one tile per workgroup.  A workgroup per compute unit (256 on an MI355X) makes the kernel 13 % faster at 2^20 rows
+ * and a proof 0.4 %, which is inside a proof's run-to-run spread -- hence not the default; the tests use small values
+ * to walk many tiles, and the column boundary, in one workgroup. */
+#define TVM_OPTION_LDE_PASS1_WORKGROUPS 10
 /* TVM_OPTION_AIR_FORK_MAX_WORKGROUPS (default 256; 0 = never): tvm_all_quotients_combined / tvm_air_class_values on a quotient domain of at
  * most this many workgroups of 256 rows launch the parts of the AIR on four streams side by side (the context's and three of its
  * own, joined before the call returns to the context's stream), and on such a domain valid-trace mode evaluates row by row. */

@@ -56,6 +56,24 @@ struct LdePlan {
     LdePass pass1, pass2, pass3;
 };
 
+// ---- pass 1's row kernels of 16-row tiles (k_lde_pass1_rows<8 | 9 | 10, 16>): persistent workgroups --------------------------------
+// A launch has `columns` x 2^log_tiles work items (column, tile), numbered tile-fastest inside a column; workgroup g of G walks the
+// items g, g + G, g + 2 G, ... -- the workgroups that run together read neighbouring 128-byte runs of one column -- and has the
+// input of its next item, if it has one, in flight while it transforms the current one.  These functions are the numbering: the kernel and the
+// host launch from them, tests/lde_pass1_grid_dump.cpp walks them.
+#if defined(__HIPCC__)
+#define TVM_PLAN_FN __host__ __device__ inline
+#else
+#define TVM_PLAN_FN inline
+#endif
+struct LdePass1Item {
+    std::uint64_t column, tile;
+};
+TVM_PLAN_FN std::uint64_t lde_pass1_items(std::uint64_t columns, int log_tiles) { return columns << log_tiles; }
+TVM_PLAN_FN LdePass1Item lde_pass1_item(std::uint64_t index, int log_tiles) {
+    return {index >> log_tiles, index & (((std::uint64_t)1 << log_tiles) - 1)};
+}
+
 inline int threads_for_tile(int tile) {
     int t = tile / 16;
     t = (t + 63) / 64 * 64;
@@ -83,6 +101,16 @@ inline LdePass lde_generic_pass(LdeKernel kernel, int log_axis, int batch_log, i
     return p;
 }
 
+// Workgroups of a launch of pass 1's persistent row kernels over `items` work items: option (TVM_OPTION_LDE_PASS1_WORKGROUPS) of them,
+// never more than there are items.  0, the default, and any count at or above the items: ONE tile per workgroup, no second trip
+// through the loop.  (Measured at 2^20 rows with a workgroup per compute unit, 256 for 6144 items: the kernel -13 %, a proof -0.4 % --
+// inside the spread of a proof's time from run to run, so the walking grid is not the default: DESIGN.md 9.)
+inline std::uint64_t lde_pass1_workgroups(std::uint64_t items, std::uint64_t option) {
+    const std::uint64_t g = option ? option : items;
+    return g < items ? g : (items ? items : 1);
+}
+inline bool is_pass1_persistent(LdeKernel k) { return k >= LdeKernel::pass1_rows_8_16 && k <= LdeKernel::pass1_rows_10_16; }
+
 inline LdePlan lde_plan(const LdePlanInput& in) {
     const int log_n1 = in.log_n / 2, log_n2 = in.log_n - log_n1;   // (so n2 >= n1: an axis long enough for a row or tile kernel
     const std::size_t n1 = (std::size_t)1 << log_n1, n2 = (std::size_t)1 << log_n2;   // always has whole tiles on the other axis)
@@ -106,8 +134,10 @@ inline LdePlan lde_plan(const LdePlanInput& in) {
 
     // pass 1: a row per 16 / 32 / 64 lanes (256 / 512 / 1024 points), 16 rows and a row of twiddles; 2048 points: two wavefronts per
     // row, 8 rows, sixteen blocks of 64 pair flags in front.
-    // (1024 points, 16-row tiles: 128-byte runs of the input.  8-row tiles -- two workgroups per CU -- measured the same time and
-    // fetch every input line twice: 16 instead of 8 B per cell, profiles/r03_q_pmc_lde.txt.)
+    // (1024 points, 16-row tiles: 128-byte runs of the input.  8-row tiles -- two workgroups per CU, one's loads under the other's
+    // butterflies -- measured the same time and fetch every input line twice: 16 instead of 8 B per cell, profiles/r03_q_pmc_lde.txt.
+    // The 16-row kernels can overlap within ONE workgroup instead -- fewer workgroups than tiles, the next tile in registers:
+    // lde_pass1_workgroups.)
     if (in.mode != TVM_LDE_FORWARD_ONLY) {
         const std::size_t words16 = 16 * TVM_ROW_WORDS(n1) + n1;
         if (in.std_roots && log_n1 == 8 && row_kernels_allowed) plan.pass1 = pass(LdeKernel::pass1_rows_8_16, 256, words16, 16);

@@ -283,6 +283,7 @@ struct Ntt2Args {
     const u64* post_hi;
     u64 out_mul, out_add;        // output element k is stored at index k*out_mul + out_add
     int col0;                    // first virtual column (in/out use col0 + blockIdx.y, tmp uses blockIdx.y)
+    int cols;                    // columns of the launch (the persistent k_lde_pass1_rows: its work items are cols x tiles)
     int root;                    // 1 / 2: w is the domains' own N-th root of unity / its inverse (shift twiddles, lds_ntt_group)
 };
 
@@ -848,11 +849,21 @@ __global__ void k_pass3_halves_table(const u64* __restrict__ tw_2048, u64* __res
 // 16 rows of 1024 points i1 (128-byte runs in memory); wavefront w transforms row w (decimation in frequency, inverse roots),
 // and the store applies the inter-pass twiddle w_N^-(i2 * k1) as a running product over k1 = brev(position) -- the positions
 // of a work-item are visited in bit-reversed order so that k1 advances by one -- instead of two table loads per element.
+//
+// The 16-row instantiations (256 .. 1024 points) take any grid: gridDim.x workgroups walk the launch's a.cols x n2 / 16 work items
+// (lde_plan.h: lde_pass1_item).  The row of twiddles goes into LDS once per workgroup, and a work-item requests the 16 input words of
+// its NEXT item as soon as the current tile is complete in LDS -- they are in flight under the butterflies and the store phase, and
+// go into LDS after it.  No barrier between the store phase and that fill: a work-item reads, in the store phase, exactly the 16
+// words (row b, positions q0 + LPR it) that it fills, so it overwrites nothing another work-item still has to read; the two
+// barriers of a tile are "tile complete" and "rows transformed".  With a workgroup per item -- the default,
+// TVM_OPTION_LDE_PASS1_WORKGROUPS = 0 -- the phases of a tile run one after the other (one workgroup per CU at 1024 points: while a
+// tile loads nothing is issued, while it is transformed nothing is in flight); with a workgroup per compute unit the kernel is
+// 13 % faster at 2^20 rows (profiles/lde_pass1_*), which a proof's time does not resolve: not the default.
 template <int LOGN, int ROWS>
 __global__ void __launch_bounds__((1 << (LOGN - 4)) * ROWS, 4) k_lde_pass1_rows(Ntt2Args a) {
     // LOGN = 10: one wavefront per row, 16 rows (128-byte runs of the input).  LOGN = 11 (round 5; 2^22 and 2^23-row traces): TWO
     // wavefronts per row of 2048 points, 8 rows (LDS holds no more of them: 64-byte runs), the butterfly groups separated by
-    // workgroup barriers (row_ntt_group, LPR = 128) -- instead of the generic k_ntt2_pass1.
+    // workgroup barriers (row_ntt_group, LPR = 128) -- instead of the generic k_ntt2_pass1; one tile per workgroup, grid = tiles x columns.
     // LOGN = 9 / 8 (round 6; 2^16 .. 2^19-row traces): 32 / 16 lanes per row, two / four rows per wavefront, 16 rows.
     constexpr int n1 = 1 << LOGN, ROWW = TVM_ROW_WORDS(n1), LPR = n1 / 16, NT = LPR * ROWS, RLOG = ROWS == 16 ? 4 : 3;
     static_assert((LOGN >= 8 && LOGN <= 10 && (ROWS == 16 || ROWS == 8)) || (LOGN == 11 && ROWS == 8), "16 .. 128 lanes per row of 256 .. 2048 points");
@@ -860,18 +871,19 @@ __global__ void __launch_bounds__((1 << (LOGN - 4)) * ROWS, 4) k_lde_pass1_rows(
     u64* const s = s_all + (LPR > 64 ? 512 : 0);   // (two wavefronts per row: sixteen blocks of 64 pair flags first, tvm_pair_sync)
     const int tid = threadIdx.x;
     const u64 n2 = 1ull << a.log_n2;
-    const int vl = blockIdx.y, v = a.col0 + vl;
-    const u64 i2_0 = (u64)blockIdx.x * ROWS;
     const int b = tid & (ROWS - 1), q0 = tid >> RLOG;   // this work-item loads / stores row b, positions q0 + LPR * it
-    const u64* in = a.in + (u64)(v / a.in_fk) * a.in_col_stride + (v % a.in_fk) + (i2_0 + b) * a.in_fk;
-#pragma unroll
-    for (int it = 0; it < 16; it++) {
-        const int i1 = q0 + LPR * it;
-        s[b * ROWW + TVM_ROW_SKEW(i1)] = TVM_LOAD_STREAM(&in[(u64)i1 * n2 * a.in_fk]);
-    }
     u64* tw_lds = s + ROWS * ROWW;
-    for (int i = tid; i < n1; i += NT) tw_lds[i] = a.tw1[i];   // all n1 powers of the inverse root
-    if constexpr (LPR > 64) {   // two wavefronts per row: the pair meets between the butterfly groups (tvm_pair_sync), not the workgroup
+    if constexpr (LPR > 64) {
+        const int vl = blockIdx.y, v = a.col0 + vl;
+        const u64 i2_0 = (u64)blockIdx.x * ROWS;
+        const u64* in = a.in + (u64)(v / a.in_fk) * a.in_col_stride + (v % a.in_fk) + (i2_0 + b) * a.in_fk;
+#pragma unroll
+        for (int it = 0; it < 16; it++) {
+            const int i1 = q0 + LPR * it;
+            s[b * ROWW + TVM_ROW_SKEW(i1)] = TVM_LOAD_STREAM(&in[(u64)i1 * n2 * a.in_fk]);
+        }
+        for (int i = tid; i < n1; i += NT) tw_lds[i] = a.tw1[i];   // all n1 powers of the inverse root
+        // two wavefronts per row: the pair meets between the butterfly groups (tvm_pair_sync), not the workgroup
         unsigned* const pair_flags = (unsigned*)s_all;
         pair_flags[tid] = 0;   // (NT = 16 x 64)
         tvm_lds_barrier();
@@ -880,22 +892,65 @@ __global__ void __launch_bounds__((1 << (LOGN - 4)) * ROWS, 4) k_lde_pass1_rows(
         int row_lane = tid % LPR;   // (tvm_pair_sync borrows its register: 64 * (wave % 2) + lane)
         auto pair = [&] { tvm_pair_sync(pair_flags, wave, wave ^ 1, ++pair_epoch, row_lane, (wave & 1) * 64); };
         row_ntt<false, 4, LOGN, 2, 0, LPR>(s + (tid / LPR) * ROWW, tw_lds, row_lane, pair);
-    } else {
         tvm_lds_barrier();
-        row_ntt<false, 4, LOGN, 2, 0, LPR>(s + (tid / LPR) * ROWW, tw_lds, tid % LPR);
-    }
-    tvm_lds_barrier();
-    // position p = q0 + LPR * brev4(c) holds index k1 = brev(p) = brev(q0) * 16 + c
-    const u64 i2 = i2_0 + b;
-    const u64 k1_0 = (u64)brev_bits((u32)q0, LOGN - 4) << 4;
-    u64 t = pow2_get(a.tw_inter, (i2 * k1_0) & ((n2 << LOGN) - 1));
-    const u64 t_step = pow2_get(a.tw_inter, i2);
-    u64* tmp = a.tmp + (u64)vl * a.tmp_col_stride + i2;
+        // position p = q0 + LPR * brev4(c) holds index k1 = brev(p) = brev(q0) * 16 + c
+        const u64 i2 = i2_0 + b;
+        const u64 k1_0 = (u64)brev_bits((u32)q0, LOGN - 4) << 4;
+        u64 t = pow2_get(a.tw_inter, (i2 * k1_0) & ((n2 << LOGN) - 1));
+        const u64 t_step = pow2_get(a.tw_inter, i2);
+        u64* tmp = a.tmp + (u64)vl * a.tmp_col_stride + i2;
 #pragma unroll 4
-    for (int c = 0; c < 16; c++) {
-        const int p = q0 + LPR * (int)brev_bits((u32)c, 4);
-        TVM_STORE_STREAM(&tmp[(u64)p * n2], bfe_mul(s[b * ROWW + TVM_ROW_SKEW(p)], t));
-        t = bfe_mul(t, t_step);
+        for (int c = 0; c < 16; c++) {
+            const int p = q0 + LPR * (int)brev_bits((u32)c, 4);
+            TVM_STORE_STREAM(&tmp[(u64)p * n2], bfe_mul(s[b * ROWW + TVM_ROW_SKEW(p)], t));
+            t = bfe_mul(t, t_step);
+        }
+    } else {
+        const int log_tiles = a.log_n2 - RLOG;
+        const u64 items = lde_pass1_items((u64)a.cols, log_tiles), G = gridDim.x;
+        const u64 in_step = n2 * (u64)a.in_fk * LPR;   // words between two of a work-item's inputs
+        // the work-item's first input word of item `index`: column v = col0 + column, row i2 = 16 tile + b, position q0
+        const auto input_of = [&](u64 index) {
+            const LdePass1Item item = lde_pass1_item(index, log_tiles);
+            const int v = a.col0 + (int)item.column;
+            return a.in + (u64)(v / a.in_fk) * a.in_col_stride + (v % a.in_fk) + ((item.tile << RLOG) + (u64)b + (u64)q0 * n2) * (u64)a.in_fk;
+        };
+        u64 index = blockIdx.x;
+        if (index >= items) return;   // (the host launches no more workgroups than items)
+        u64 nxt[16];
+        {
+            const u64* in = input_of(index);
+#pragma unroll
+            for (int it = 0; it < 16; it++) nxt[it] = TVM_LOAD_STREAM(&in[(u64)it * in_step]);
+        }
+        for (int i = tid; i < n1; i += NT) tw_lds[i] = a.tw1[i];   // all n1 powers of the inverse root: once per workgroup
+        u64* const mine = s + b * ROWW + TVM_ROW_SKEW(q0);         // TVM_ROW_SKEW(q0 + LPR it) = TVM_ROW_SKEW(q0) + TVM_ROW_SKEW(LPR it): LPR = 0 (mod 16)
+        const u64 k1_0 = (u64)brev_bits((u32)q0, LOGN - 4) << 4;
+#pragma unroll 1
+        for (; index < items; index += G) {
+#pragma unroll
+            for (int it = 0; it < 16; it++) mine[TVM_ROW_SKEW(LPR * it)] = nxt[it];
+            tvm_lds_barrier();   // the tile is complete
+            if (index + G < items) {   // the next item's inputs: requested now, used after the store phase (no address is formed past the last item)
+                const u64* in = input_of(index + G);
+#pragma unroll
+                for (int it = 0; it < 16; it++) nxt[it] = TVM_LOAD_STREAM(&in[(u64)it * in_step]);
+            }
+            row_ntt<false, 4, LOGN, 2, 0, LPR>(s + (tid / LPR) * ROWW, tw_lds, tid % LPR);
+            tvm_lds_barrier();   // the rows are transformed
+            // position p = q0 + LPR * brev4(c) holds index k1 = brev(p) = brev(q0) * 16 + c
+            const LdePass1Item item = lde_pass1_item(index, log_tiles);
+            const u64 i2 = (item.tile << RLOG) + (u64)b;
+            u64 t = pow2_get(a.tw_inter, (i2 * k1_0) & ((n2 << LOGN) - 1));
+            const u64 t_step = pow2_get(a.tw_inter, i2);
+            u64* tmp = a.tmp + item.column * a.tmp_col_stride + i2;
+#pragma unroll 4
+            for (int c = 0; c < 16; c++) {
+                const int p = q0 + LPR * (int)brev_bits((u32)c, 4);
+                TVM_STORE_STREAM(&tmp[(u64)p * n2], bfe_mul(s[b * ROWW + TVM_ROW_SKEW(p)], t));
+                t = bfe_mul(t, t_step);
+            }
+        }
     }
 }
 
@@ -1301,6 +1356,7 @@ static int ntt2_common(tvm_ctx* c, u64 w, u64 n, const Split& sp, Ntt2Args* a) {
     a->out_mul = 1;
     a->out_add = 0;
     a->col0 = 0;
+    a->cols = 0;
     return TVM_OK;
 }
 
@@ -1481,7 +1537,11 @@ int lde_table(tvm_ctx* c, int fk, const u64* trace, u64 n_rows, u64 n_cols, cons
             const LdePass& s = plan.pass1;
             Ntt2Args a = p1;
             a.col0 = col0;
-            TVM_LAUNCH(variant_of(s.kernel).ntt2, dim3(tiles_of(n2, s.rows), (unsigned)nc), dim3(s.block), s.lds_bytes, c->stream, a);
+            a.cols = nc;
+            dim3 grid(tiles_of(n2, s.rows), (unsigned)nc);
+            if (is_pass1_persistent(s.kernel))   // a one-dimensional grid over the chunk's (column, tile) items: one workgroup each, or fewer
+                grid = dim3((unsigned)lde_pass1_workgroups((u64)nc * tiles_of(n2, s.rows), c->lde_pass1_workgroups));
+            TVM_LAUNCH(variant_of(s.kernel).ntt2, grid, dim3(s.block), s.lds_bytes, c->stream, a);
         }
         {
             LdePass s = plan.pass2;
