@@ -158,6 +158,12 @@ int32_t tvm_synthetic_fill(tvm_ctx* ctx, uint64_t* d_data, uint64_t n_words, uin
  * 2^K points with power-of-two twiddles on consecutive groups of 2^K words of d_a (d_b unused): dit = bit-reversed in /
  * natural out, else natural in / bit-reversed out; inverse = with the inverse root (no scaling by 2^-K). */
 int32_t tvm_field_op(tvm_ctx* ctx, int32_t op, const uint64_t* d_a, const uint64_t* d_b, uint64_t* d_out, uint64_t n);
+/* The 16-point transform with power-of-two twiddles (decimation in time: bit-reversed in, natural out, no scaling) on n_groups
+ * consecutive groups of 16 words, in the two forms the device has: form bit 0 = with the inverse root, bit 1 = on the matrix cores
+ * (csrc/ntt_mfma.h; clear: the shift form of csrc/ntt_shift.h, canonical inputs only), bit 2 (matrix cores only) = the output as
+ * folded 64-bit representatives of the residues instead of canonical words.  The matrix-core form takes ANY 64-bit words as inputs.
+ * The known-answer hook of csrc/ntt_mfma.h (tests/test_dft16_mfma.py). */
+int32_t tvm_dft16_selfcheck(tvm_ctx* ctx, int32_t form, const uint64_t* d_in, uint64_t* d_out, uint64_t n_groups);
 
 /* ---- L2 / L3: ArithmeticDomain::{evaluate, interpolate} (arithmetic_domain.rs:141-189) -------
  * d_coeffs: n_coeffs elements, d_values: domain.length elements, both arrays of field_kind-word

@@ -6,6 +6,7 @@
 #include <vector>
 
 #include "kernels.h"
+#include "ntt_mfma.h"
 #include "ntt_shift.h"
 
 using namespace tvm;
@@ -98,6 +99,58 @@ int32_t tvm_field_op(tvm_ctx* c, int32_t op, const uint64_t* d_a, const uint64_t
         return TVM_OK;
     }
     TVM_LAUNCH(tvm::k_field_op, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, (int)op, d_a, d_b, d_out, n);
+    TVM_HIP_CHECK(c, hipGetLastError());
+    return TVM_OK;
+}
+
+// ---------------------------------------------------------------------------------- the 16-point transform on the matrix cores
+}  // extern "C"
+namespace tvm {
+TVM_CONST_TABLE Dft16MfmaTable d_dft16_dit_forward = dft16_make_mfma_table(Pow2Root<4, false>::value, dft16_layout_dit());
+TVM_CONST_TABLE Dft16MfmaTable d_dft16_dit_inverse = dft16_make_mfma_table(Pow2Root<4, true>::value, dft16_layout_dit());
+// ntt_mfma.h on consecutive groups of 16 words, decimation in time (bit-reversed in, natural out): a wavefront takes 64 groups as four
+// sets of sixteen, lane (n, g) the words 4g .. 4g+3 of group 16 * set + n.  The groups past the end are computed on the last group's
+// words (every lane takes part in the matrix instructions) and not stored.
+template <bool INVERSE, bool CANONICAL>
+__global__ void __launch_bounds__(256) k_dft16_mfma(const u64* __restrict__ a, u64* __restrict__ out, u64 n_groups) {
+    __shared__ __attribute__((aligned(16))) u32 tab_words[sizeof(Dft16MfmaTable) / 4];
+    const u32* src = (const u32*)(INVERSE ? &d_dft16_dit_inverse : &d_dft16_dit_forward);
+    for (int i = threadIdx.x; i < (int)(sizeof(Dft16MfmaTable) / 4); i += blockDim.x) tab_words[i] = src[i];
+    __syncthreads();
+    const int lane = threadIdx.x & 63, n = lane & 15, g = lane >> 4;
+    const Dft16OperandsAt m{(const Dft16MfmaTable*)tab_words, lane};
+    const u64 wave = (u64)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+    for (int set = 0; set < 4; set++) {
+        const u64 group = wave * 64 + 16 * set + n, from = group < n_groups ? group : n_groups - 1;
+        u64 x[4];
+#pragma unroll
+        for (int t = 0; t < 4; t++) x[t] = a[16 * from + 4 * g + t];
+        dft16_mfma<CANONICAL>(x, m);
+        if (group < n_groups) {
+#pragma unroll
+            for (int t = 0; t < 4; t++) out[16 * group + 4 * g + t] = x[t];
+        }
+    }
+}
+}  // namespace tvm
+extern "C" {
+int32_t tvm_dft16_selfcheck(tvm_ctx* c, int32_t form, const uint64_t* d_in, uint64_t* d_out, uint64_t n_groups) {
+    if (!c || form < 0 || form > 7 || ((form & 4) && !(form & 2)) || (n_groups && (!d_in || !d_out)))
+        return set_error(c, TVM_ERR_INVALID_ARGUMENT, "tvm_dft16_selfcheck arguments");
+    if (!n_groups) return TVM_OK;
+    const int inverse = form & 1;
+    if (!(form & 2)) {
+        tvm::launch_pow2_points<4>(c, 1, inverse, d_in, d_out, n_groups);
+    } else {
+        const dim3 grid((unsigned)((n_groups + 255) / 256)), block(256);
+        if (form & 4) {
+            if (inverse) TVM_LAUNCH((tvm::k_dft16_mfma<true, false>), grid, block, 0, c->stream, d_in, d_out, n_groups);
+            else TVM_LAUNCH((tvm::k_dft16_mfma<false, false>), grid, block, 0, c->stream, d_in, d_out, n_groups);
+        } else {
+            if (inverse) TVM_LAUNCH((tvm::k_dft16_mfma<true, true>), grid, block, 0, c->stream, d_in, d_out, n_groups);
+            else TVM_LAUNCH((tvm::k_dft16_mfma<false, true>), grid, block, 0, c->stream, d_in, d_out, n_groups);
+        }
+    }
     TVM_HIP_CHECK(c, hipGetLastError());
     return TVM_OK;
 }

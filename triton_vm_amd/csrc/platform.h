@@ -130,6 +130,13 @@ typedef unsigned long tvm_u64v2 __attribute__((ext_vector_type(2)));
 #define TVM_STORE_STREAM_X2(ptr, a, b) __builtin_nontemporal_store(tvm_u64v2{(a), (b)}, (tvm_u64v2*)(ptr))
 #endif
 
+// A constant table in device memory (the emulation: in host memory).
+#ifdef TVM_EMU
+#define TVM_CONST_TABLE static const
+#else
+#define TVM_CONST_TABLE static __device__ const
+#endif
+
 #include <cstdint>
 
 typedef uint64_t u64;

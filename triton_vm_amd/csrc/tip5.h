@@ -10,6 +10,7 @@
 // the 32-bit halves of each word, with one reduction per output (tip-0005.md:101-103).
 #pragma once
 #include "field.h"
+#include "mfma_i8.h"
 #include "tip5_tables.h"
 
 #define TIP5_STATE 16
@@ -19,12 +20,7 @@
 
 // Constant tables.  The round constants are read with wave-uniform indices (scalar loads); the
 // 256-byte S-box table is copied into LDS by each workgroup (tip5_stage_lut) because its index is
-// per-lane data.
-#ifdef TVM_EMU
-#define TVM_CONST_TABLE static const
-#else
-#define TVM_CONST_TABLE static __device__ const
-#endif
+// per-lane data.  (TVM_CONST_TABLE: platform.h)
 TVM_CONST_TABLE u64 d_tip5_rc[80] = {TVM_TIP5_RC_LIST};
 TVM_CONST_TABLE unsigned char d_tip5_lut[256] = {TVM_TIP5_LUT_LIST};
 
@@ -178,34 +174,7 @@ TVM_D u64 tip5_permute_lanes(u64 x, int pos, int lane, const unsigned char* lut)
 //
 // The remaining VALU work per word is the recombination of ten 22-bit sums into one field element (tip5_mfma_recombine: five shift-adds,
 // three multiply-adds and a carry tail of four or six instructions), against ~62 for the all-VALU form.
-#ifdef TVM_EMU
-struct tvm_v4i {
-    int v[4];
-    int& operator[](int i) { return v[i]; }
-    const int& operator[](int i) const { return v[i]; }
-};
-// v_mfma_i32_16x16x64_i8 as this file relies on it: lane (i = l % 16, q = l / 16) supplies 16 signed bytes of row i
-// of A and of column i of B for the same sixteen k-indices (which sixteen is irrelevant to a sum over k), and
-// receives D[4q + v][i] = C + sum_k A[4q + v][k] B[k][i] in element v.  The GPU parity tests of tvm_hash_rows
-// (tests/test_kernels_hash.py) run the same kernel on the hardware: they fail if it differs from this model.
-static inline tvm_v4i emu_mfma_i32_16x16x64_i8(tvm_v4i a, tvm_v4i b, tvm_v4i c) {
-    struct { tvm_v4i a, b; } mine = {a, b}, all[64];
-    emu_wave_gather(&mine, sizeof(mine), all);
-    const int lane = emu::lane_id(), col = lane & 15, q = lane >> 4;
-    tvm_v4i d = c;
-    for (int v = 0; v < 4; v++)
-        for (int kq = 0; kq < 4; kq++) {
-            const signed char* pa = (const signed char*)&all[16 * kq + 4 * q + v].a;
-            const signed char* pb = (const signed char*)&all[16 * kq + col].b;
-            for (int k = 0; k < 16; k++) d[v] += (int)pa[k] * (int)pb[k];
-        }
-    return d;
-}
-#define TVM_MFMA_I8(a, b, c) emu_mfma_i32_16x16x64_i8((a), (b), (c))
-#else
-typedef int tvm_v4i __attribute__((ext_vector_type(4)));
-#define TVM_MFMA_I8(a, b, c) __builtin_amdgcn_mfma_i32_16x16x64_i8((a), (b), (c), 0, 0, 0)
-#endif
+// (the instruction, and the model of it that the CPU emulation runs: mfma_i8.h)
 
 #define TIP5_MFMA_POSITIONS 10
 #define TIP5_MFMA_BIAS_LOG 21
