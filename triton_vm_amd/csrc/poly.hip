@@ -45,14 +45,78 @@ TVM_D xfe block_sum_xfe(xfe v, u64* smem, int tid, int nt) {
 // ------------------------------------------------------------------------------------------------
 // Out-of-domain rows (master_table.rs:348-390), for n_points indeterminates at once.
 // u[p][j] = d_j / (alpha_p - d_j), d_j = gen^j (trace domain, offset 1)
-__global__ void k_ood_weights(u64 gen, u64 n, const u64* __restrict__ points, int n_points, u64* __restrict__ u) {
-    const u64 j = (u64)blockIdx.x * blockDim.x + threadIdx.x;
-    if (j >= n) return;
-    const u64 d = bfe_pow(gen, j);
+//
+// Inverses of extension-field elements a = (a0, a1, a2) that share a1 and a2 (alpha - d_j here, x_i - point in DEEP), through the
+// base field: 1 / a = adj(a) / N(a) with xfe_inv's adjugate (k0, k1, k2) and norm N = a0 k0 - a2 k1 - a1 k2 in F_p.  With
+// s = a0 + a2:  k0 = s^2 - e,  k1 = f - a1 s,  k2 = g - a2 s,  where e = (a1 - a2) a1, f = (a1 - a2) a2, g = a1^2 are fixed:
+// three products for the adjugate and three for the norm.  A batch of such inverses then needs ONE bfe_inv (Montgomery's trick
+// over the norms, three bfe products per element) where xfe_inv per element takes one each.  All of it is exact field arithmetic:
+// the words are those of xfe_inv.
+struct FixedTail {
+    u64 a1, a2, e, f, g;
+};
+// (the products are vector instructions on operands every lane shares: tvm_uniform hands the results back to scalar registers)
+TVM_D u64 uniform_u64(u64 v) { return ((u64)(u32)tvm_uniform((int)(u32)(v >> 32)) << 32) | (u32)tvm_uniform((int)(u32)v); }
+TVM_D FixedTail fixed_tail(u64 a1, u64 a2) {
+    FixedTail d;
+    d.a1 = a1, d.a2 = a2;
+    const u64 d12 = bfe_sub(a1, a2);
+    bfe_mul3(d12, a1, d12, a2, a1, a1, d.e, d.f, d.g);
+    d.e = uniform_u64(d.e), d.f = uniform_u64(d.f), d.g = uniform_u64(d.g);
+    return d;
+}
+TVM_D xfe tail_adjugate(u64 a0, const FixedTail& d) {
+    const u64 s = bfe_add(a0, d.a2);
+    u64 ss, t1, t2;
+    bfe_mul3(s, s, d.a1, s, s, d.a2, ss, t1, t2);
+    u64 k0, k1, k2;
+    bfe_sub3(ss, d.e, d.f, t1, d.g, t2, k0, k1, k2);
+    return xfe_make(k0, k1, k2);
+}
+TVM_D u64 tail_norm(u64 a0, const FixedTail& d, xfe adj) {
+    u64 m0, m1, m2;
+    bfe_mul3(a0, adj.c0, d.a2, adj.c1, d.a1, adj.c2, m0, m1, m2);
+    return bfe_sub(bfe_sub(m0, m1), m2);
+}
+// A work-item takes `run` (<= TVM_OOD_RUN) rows, n / run apart -- consecutive work-items write consecutive rows -- so d_j is one
+// bfe_pow and then a running product with gen^(n / run), and one bfe_inv serves the run's denominators of a point (one bfe_pow and
+// one xfe_inv per row and point before: 0.19 ms per proof at 2^20 rows).  alpha - d_j = 0 cannot occur in a proof (alpha is not in
+// the base field); its norm is zero and the weights of the work-item's whole run for that point come out zero (one weight before).
+#define TVM_OOD_RUN 8
+__global__ void __launch_bounds__(256) k_ood_weights(u64 gen, u64 n, int run, const u64* __restrict__ points, int n_points,
+                                                     u64* __restrict__ u) {
+    const u64 t = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+    const u64 stride = n / (u64)run;   // work-items; n and run are powers of two
+    if (t >= stride) return;
+    u64 d[TVM_OOD_RUN];
+    d[0] = bfe_pow(gen, t);
+    const u64 step = bfe_pow(gen, stride);
+#pragma unroll
+    for (int i = 1; i < TVM_OOD_RUN; i++) d[i] = bfe_mul(d[i - 1], step);
     for (int p = 0; p < n_points; p++) {
-        xfe a = ld_xfe(points + 3 * p);
-        xfe inv = xfe_inv(xfe_sub_bfe(a, d));
-        st_xfe(u + ((u64)p * n + j) * 3, xfe_mul_bfe(inv, d));
+        const xfe a = ld_xfe(points + 3 * p);
+        const FixedTail tail = fixed_tail(a.c1, a.c2);
+        u64 pre[TVM_OOD_RUN];
+        u64 prod = TVM_ONE;
+#pragma unroll
+        for (int i = 0; i < TVM_OOD_RUN; i++) {
+            pre[i] = prod;
+            if (i < run) {
+                const u64 a0 = bfe_sub(a.c0, d[i]);
+                prod = bfe_mul(prod, tail_norm(a0, tail, tail_adjugate(a0, tail)));
+            }
+        }
+        u64 inv = bfe_inv(prod);
+#pragma unroll
+        for (int i = TVM_OOD_RUN - 1; i >= 0; i--) {
+            if (i < run) {
+                const u64 a0 = bfe_sub(a.c0, d[i]);
+                const xfe adj = tail_adjugate(a0, tail);
+                u64 ninv;
+                bfe_mul2(inv, pre[i], inv, tail_norm(a0, tail, adj), ninv, inv);
+                st_xfe(u + ((u64)p * n + t + (u64)i * stride) * 3, xfe_mul_bfe(adj, bfe_mul(ninv, d[i])));
+            }
+        }
     }
 }
 // partial[p][c][chunk] = sum over the rows j of the chunk of cell(c, j) * u[p][j]; column index n_cols is the
@@ -86,27 +150,68 @@ __global__ void __launch_bounds__(TVM_RED_BLOCK) k_column_dot(const u64* __restr
 #pragma unroll
         for (int g = 0; g < G; g++) acc[g][q] = air_acc_zero();
     }
-    for (u64 j = r0 + tid; j < r1; j += nt) {
+    // Base-field table: the operands of a row -- its weights and its G cells -- are loaded one row AHEAD of the products (two sets,
+    // used in turn).  With the loads at the head of the row's own products a wavefront waited out a memory latency per 156
+    // instructions, and three wavefronts per SIMD do not cover it: 1.52 ms per proof at 2^20 rows where the products issue in 0.8.
+    // (An extension-field row has 234 instructions per load and measured no faster this way: it keeps the plain loop.)
+    constexpr bool AHEAD = FK == 1;
+    struct Row {
         xfe w[TVM_DOT_P];
+        u64 x[G][FK];
+    };
+    auto load = [&](u64 j, Row& r) {
 #pragma unroll
-        for (int q = 0; q < TVM_DOT_P; q++) w[q] = (q < np) ? ld_xfe(u + ((u64)(p0 + q) * n + j) * 3) : xfe_zero();
+        for (int q = 0; q < TVM_DOT_P; q++) r.w[q] = (q < np) ? ld_xfe(u + ((u64)(p0 + q) * n + j) * 3) : xfe_zero();
+#pragma unroll
+        for (int g = 0; g < G; g++)
+#pragma unroll
+            for (int k = 0; k < FK; k++) r.x[g][k] = (c0 + g < n_cols) ? trace[((c0 + g) * n + j) * FK + k] : 0;
+    };
+    auto accumulate = [&](const Row& r) {
 #pragma unroll
         for (int g = 0; g < G; g++) {
             const u64 c = c0 + g;
             if (c < n_cols) {
-                const u64* cp = trace + (c * n + j) * FK;
-                if constexpr (FK == 1) {
-                    const u64 x = cp[0];
 #pragma unroll
-                    for (int q = 0; q < TVM_DOT_P; q++) air_acc_b(acc[g][q], w[q], x);
-                } else {
-                    const xfe x = ld_xfe(cp);
-#pragma unroll
-                    for (int q = 0; q < TVM_DOT_P; q++) air_acc_x(acc[g][q], w[q], x);
+                for (int q = 0; q < TVM_DOT_P; q++) {
+                    if constexpr (FK == 1) air_acc_b(acc[g][q], r.w[q], r.x[g][0]);
+                    else air_acc_x(acc[g][q], r.w[q], xfe_make(r.x[g][0], r.x[g][1], r.x[g][2]));
                 }
             } else if (c == n_cols) {
 #pragma unroll
-                for (int q = 0; q < TVM_DOT_P; q++) ones[q] = xfe_add(ones[q], w[q]);
+                for (int q = 0; q < TVM_DOT_P; q++) ones[q] = xfe_add(ones[q], r.w[q]);
+            }
+        }
+    };
+    u64 j = r0 + tid;
+    if constexpr (AHEAD) {
+        Row ra, rb;
+        if (j < r1) load(j, ra);
+        while (j < r1) {
+            if (j + nt < r1) load(j + nt, rb);
+            accumulate(ra);
+            j += nt;
+            if (j >= r1) break;
+            if (j + nt < r1) load(j + nt, ra);
+            accumulate(rb);
+            j += nt;
+        }
+    } else {
+        for (; j < r1; j += nt) {
+            xfe w[TVM_DOT_P];
+#pragma unroll
+            for (int q = 0; q < TVM_DOT_P; q++) w[q] = (q < np) ? ld_xfe(u + ((u64)(p0 + q) * n + j) * 3) : xfe_zero();
+#pragma unroll
+            for (int g = 0; g < G; g++) {
+                const u64 c = c0 + g;
+                if (c < n_cols) {
+                    const xfe x = ld_xfe(trace + (c * n + j) * FK);
+#pragma unroll
+                    for (int q = 0; q < TVM_DOT_P; q++) air_acc_x(acc[g][q], w[q], x);
+                } else if (c == n_cols) {
+#pragma unroll
+                    for (int q = 0; q < TVM_DOT_P; q++) ones[q] = xfe_add(ones[q], w[q]);
+                }
             }
         }
     }
@@ -386,11 +491,14 @@ struct DeepArgs {
     u64* out;
 };
 // Four points per work-item, a quarter of the domain apart: x_{i + j n/4} = x_i w^j with w = gen^(n/4) a fourth root of unity, so
-// one power of the generator serves four points, and ONE inversion the 4 n_comp denominators of all of them (Montgomery's
-// trick; the denominators are recomputed on the way back instead of kept: sixteen prefix products are what the registers hold).
-// (Measured: the steps written out for four components -- no run-time indexing of the prefix products, which hipcc keeps in
-// 400 bytes of scratch here -- need 225 VGPRs and run 11 % slower, 1.07 vs 0.96 ms at 2^23 points; the kernel issues ~4700
-// instructions per point and is within 10 % of that issue time as it stands.)
+// one power of the generator serves four points, and ONE inversion the 4 n_comp denominators of all of them -- in the BASE field
+// (FixedTail above: x - p = (x - p0, -p1, -p2) shares its two upper coefficients over the points x): Montgomery's trick runs over
+// the sixteen norms, three bfe products per denominator and one bfe_inv per work-item, where prefix products of the denominators
+// themselves took three xfe products -- 27 -- and an xfe_inv.  The prefix products are sixteen words in registers (the xfe
+// prefixes were 400 bytes of scratch); adjugate and norm are recomputed on the way back (six products) instead of kept.  The
+// weighted terms of a point are summed unreduced (AirAcc).
+// A zero denominator (it cannot occur in a proof: the points are not in the base field) has norm zero: the product of the norms
+// and with it EVERY term of the work-item's four points comes out zero, as with the xfe prefix products before.
 #define TVM_DEEP_POINTS 4
 __global__ void __launch_bounds__(256) k_deep(DeepArgs a) {
     const u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
@@ -401,35 +509,40 @@ __global__ void __launch_bounds__(256) k_deep(DeepArgs a) {
     x[0] = bfe_mul(a.offset, bfe_pow(a.gen, i));
 #pragma unroll
     for (int j = 1; j < TVM_DEEP_POINTS; j++) x[j] = bfe_mul(x[j - 1], w);
-    xfe pre[TVM_DEEP_POINTS][TVM_DEEP_MAX];
-    xfe run = xfe_one();
+    FixedTail pt[TVM_DEEP_MAX];
+#pragma unroll
+    for (int k = 0; k < TVM_DEEP_MAX; k++) pt[k] = fixed_tail(bfe_neg(a.point[k][1]), bfe_neg(a.point[k][2]));
+    u64 pre[TVM_DEEP_POINTS][TVM_DEEP_MAX];
+    u64 run = TVM_ONE;
 #pragma unroll
     for (int j = 0; j < TVM_DEEP_POINTS; j++) {
 #pragma unroll
         for (int k = 0; k < TVM_DEEP_MAX; k++) {
+            pre[j][k] = run;
             if (k < a.n_comp) {
-                pre[j][k] = run;
-                run = xfe_mul(run, xfe_bfe_minus(x[j], xfe_make(a.point[k][0], a.point[k][1], a.point[k][2])));
+                const u64 a0 = bfe_sub(x[j], a.point[k][0]);
+                run = bfe_mul(run, tail_norm(a0, pt[k], tail_adjugate(a0, pt[k])));
             }
         }
     }
-    xfe inv = xfe_inv(run);
+    u64 inv = bfe_inv(run);
 #pragma unroll
     for (int j = TVM_DEEP_POINTS - 1; j >= 0; j--) {
-        xfe acc = xfe_zero();
+        AirAcc acc = air_acc_zero();
         const u64 row = i + (u64)j * quarter;
 #pragma unroll
         for (int k = TVM_DEEP_MAX - 1; k >= 0; k--) {
             if (k < a.n_comp) {
-                const xfe den = xfe_bfe_minus(x[j], xfe_make(a.point[k][0], a.point[k][1], a.point[k][2]));
-                const xfe dinv = xfe_mul(inv, pre[j][k]);
-                inv = xfe_mul(inv, den);
+                const u64 a0 = bfe_sub(x[j], a.point[k][0]);
+                const xfe adj = tail_adjugate(a0, pt[k]);
+                u64 ninv;
+                bfe_mul2(inv, pre[j][k], inv, tail_norm(a0, pt[k], adj), ninv, inv);
                 const xfe num = xfe_sub(ld_xfe(a.cw[k] + 3 * row), xfe_make(a.value[k][0], a.value[k][1], a.value[k][2]));
                 const xfe wk = xfe_make(a.weight[k][0], a.weight[k][1], a.weight[k][2]);
-                acc = xfe_add(acc, xfe_mul(xfe_mul(num, dinv), wk));
+                air_acc_x(acc, wk, xfe_mul(num, xfe_mul_bfe(adj, ninv)));
             }
         }
-        st_xfe(a.out + 3 * row, acc);
+        st_xfe(a.out + 3 * row, air_acc_value(acc));
     }
 }
 // a domain shorter than four points: one point per work-item
@@ -477,7 +590,8 @@ int out_of_domain_rows(tvm_ctx* c, int fk, const u64* trace, u64 n, u64 n_cols, 
     u64* u = (u64*)scratch(c, Scratch::OodWeights, (size_t)n_points * n * 3 * sizeof(u64));
     u64* num = (u64*)scratch(c, Scratch::OodSums, (size_t)n_points * (n_cols + 1) * 3 * sizeof(u64));
     if (!u || !num) return set_error(c, TVM_ERR_OUT_OF_MEMORY, "ood scratch");
-    TVM_LAUNCH(k_ood_weights, TVM_GRID(n, 256), dim3(256), 0, c->stream, trace_gen, n, d_points, n_points, u);
+    const int run = n < TVM_OOD_RUN ? (int)n : TVM_OOD_RUN;
+    TVM_LAUNCH(k_ood_weights, TVM_GRID(n / run, 256), dim3(256), 0, c->stream, trace_gen, n, run, d_points, n_points, u);
     // rows in chunks of 2^15 (128 rows per work-item), columns in groups of G (2 columns: the accumulators' registers and the
     // wavefronts per SIMD they leave), points two at a time (2^13 for narrow tables so that the grid still fills the chip)
     // (measured at 2^20 rows, both points, main + aux: 4 / 2 columns per workgroup 4.58 ms, 2 / 2 4.07 ms)

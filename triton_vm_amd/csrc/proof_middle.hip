@@ -14,6 +14,7 @@
 #include <cstring>
 #include <vector>
 
+#include "air_eval.h"   // AirAcc: the weighted terms of a DEEP point summed unreduced
 #include "context.h"
 #include "kernels.h"
 #include "tail_kernels.h"
@@ -135,7 +136,7 @@ __global__ void __launch_bounds__(64) k_weight_vectors(WeightVectorsArgs g) {
 // at kernel entry: the addresses are uniform and the arrays are only read, so the loads are scalar and the operands sit where the
 // kernel arguments of k_deep sit.  The bodies are restated here and not shared through a header: k_deep is issue-bound, and calling
 // its body as a function of a header -- the argument struct by reference or by value -- changed its registers in poly.hip's code
-// object (102 -> 75 VGPRs, 8 -> 32 spilled SGPRs); poly.hip stays as it is (profiles/device_middle_kernel_static_properties.txt).
+// object (profiles/device_middle_kernel_static_properties.txt; the bodies of today: profiles/ood_deep_kernel_static_properties.txt).
 #define TVM_DEEP_MAX 4
 #define TVM_DEEP_POINTS 4
 struct DeepDeviceArgs {
@@ -159,7 +160,35 @@ TVM_D DeepOperands deep_operands(const DeepDeviceArgs& a) {
     }
     return o;
 }
-// Four points per work-item, a quarter of the domain apart, one inversion for their 4 n_comp denominators (see k_deep).
+// The denominators x - p = (x - p0, -p1, -p2) inverted through the base field (poly.hip: FixedTail and its functions, restated
+// here with the kernel body): adjugate and norm with the point's two upper coefficients fixed.
+struct PmFixedTail {
+    u64 a1, a2, e, f, g;   // e = (a1 - a2) a1, f = (a1 - a2) a2, g = a1^2
+};
+TVM_D u64 pm_uniform_u64(u64 v) { return ((u64)(u32)tvm_uniform((int)(u32)(v >> 32)) << 32) | (u32)tvm_uniform((int)(u32)v); }
+TVM_D PmFixedTail pm_fixed_tail(u64 a1, u64 a2) {
+    PmFixedTail d;
+    d.a1 = a1, d.a2 = a2;
+    const u64 d12 = bfe_sub(a1, a2);
+    bfe_mul3(d12, a1, d12, a2, a1, a1, d.e, d.f, d.g);
+    d.e = pm_uniform_u64(d.e), d.f = pm_uniform_u64(d.f), d.g = pm_uniform_u64(d.g);
+    return d;
+}
+TVM_D xfe pm_tail_adjugate(u64 a0, const PmFixedTail& d) {
+    const u64 s = bfe_add(a0, d.a2);
+    u64 ss, t1, t2;
+    bfe_mul3(s, s, d.a1, s, s, d.a2, ss, t1, t2);
+    u64 k0, k1, k2;
+    bfe_sub3(ss, d.e, d.f, t1, d.g, t2, k0, k1, k2);
+    return xfe_make(k0, k1, k2);
+}
+TVM_D u64 pm_tail_norm(u64 a0, const PmFixedTail& d, xfe adj) {
+    u64 m0, m1, m2;
+    bfe_mul3(a0, adj.c0, d.a2, adj.c1, d.a1, adj.c2, m0, m1, m2);
+    return bfe_sub(bfe_sub(m0, m1), m2);
+}
+// Four points per work-item, a quarter of the domain apart, one base-field inversion for the norms of their 4 n_comp denominators
+// (see k_deep; a zero denominator zeroes every term of the work-item's four points there and here).
 __global__ void __launch_bounds__(256) k_deep_dev(DeepDeviceArgs a) {
     const u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
     const u64 quarter = a.n / TVM_DEEP_POINTS;
@@ -170,34 +199,39 @@ __global__ void __launch_bounds__(256) k_deep_dev(DeepDeviceArgs a) {
     x[0] = bfe_mul(a.offset, bfe_pow(a.gen, i));
 #pragma unroll
     for (int j = 1; j < TVM_DEEP_POINTS; j++) x[j] = bfe_mul(x[j - 1], w);
-    xfe pre[TVM_DEEP_POINTS][TVM_DEEP_MAX];
-    xfe run = xfe_one();
+    PmFixedTail pt[TVM_DEEP_MAX];
+#pragma unroll
+    for (int k = 0; k < TVM_DEEP_MAX; k++) pt[k] = pm_fixed_tail(bfe_neg(o.point[k].c1), bfe_neg(o.point[k].c2));
+    u64 pre[TVM_DEEP_POINTS][TVM_DEEP_MAX];
+    u64 run = TVM_ONE;
 #pragma unroll
     for (int j = 0; j < TVM_DEEP_POINTS; j++) {
 #pragma unroll
         for (int k = 0; k < TVM_DEEP_MAX; k++) {
+            pre[j][k] = run;
             if (k < a.n_comp) {
-                pre[j][k] = run;
-                run = xfe_mul(run, xfe_bfe_minus(x[j], o.point[k]));
+                const u64 a0 = bfe_sub(x[j], o.point[k].c0);
+                run = bfe_mul(run, pm_tail_norm(a0, pt[k], pm_tail_adjugate(a0, pt[k])));
             }
         }
     }
-    xfe inv = xfe_inv(run);
+    u64 inv = bfe_inv(run);
 #pragma unroll
     for (int j = TVM_DEEP_POINTS - 1; j >= 0; j--) {
-        xfe acc = xfe_zero();
+        AirAcc acc = air_acc_zero();
         const u64 row = i + (u64)j * quarter;
 #pragma unroll
         for (int k = TVM_DEEP_MAX - 1; k >= 0; k--) {
             if (k < a.n_comp) {
-                const xfe den = xfe_bfe_minus(x[j], o.point[k]);
-                const xfe dinv = xfe_mul(inv, pre[j][k]);
-                inv = xfe_mul(inv, den);
+                const u64 a0 = bfe_sub(x[j], o.point[k].c0);
+                const xfe adj = pm_tail_adjugate(a0, pt[k]);
+                u64 ninv;
+                bfe_mul2(inv, pre[j][k], inv, pm_tail_norm(a0, pt[k], adj), ninv, inv);
                 const xfe num = xfe_sub(pm_ld(a.cw[k] + 3 * row), o.value[k]);
-                acc = xfe_add(acc, xfe_mul(xfe_mul(num, dinv), o.weight[k]));
+                air_acc_x(acc, o.weight[k], xfe_mul(num, xfe_mul_bfe(adj, ninv)));
             }
         }
-        pm_st(a.out + 3 * row, acc);
+        pm_st(a.out + 3 * row, air_acc_value(acc));
     }
 }
 // a domain shorter than four points: one point per work-item
