@@ -108,6 +108,12 @@ int32_t tvm_ctx_trim(tvm_ctx* ctx);
 /* TVM_OPTION_AIR_CHECK_CHUNK_ROWS: rows per chunk of tvm_check_constraints (a power of two in 16 .. 2^20; default 2^18, 0 restores it)
  * -- the tests lower it to reach the chunk boundaries with small traces.  The same report for every value. */
 #define TVM_OPTION_AIR_CHECK_CHUNK_ROWS 9
+/* TVM_OPTION_SEGMENTS_FROM_COEFFICIENTS (default 1): tvm_quotient_segments(_from_coefficients) hands the segment polynomials to the
+ * table extension as coefficients -- one relayout pass, then the forward half of the extension -- where the LDT domain has 2 to 32
+ * times n points and at least as many as a segment has coefficients; n is the largest power of two (at least 16) in a segment's
+ * length max(n_coeffs / 4, n_rand), the coefficients beyond n are the randomizer part of the extension.  0: the segments' values on
+ * the roots of unity first and the whole extension from there (A/B).  The same words either way. */
+#define TVM_OPTION_SEGMENTS_FROM_COEFFICIENTS 11
 int32_t tvm_ctx_set_option(tvm_ctx* ctx, int32_t option, uint64_t value);
 /* Cap on the bytes this context may hold through tvm_malloc / table handles (0 = no cap).  Requests beyond it fail
  * with TVM_ERR_OUT_OF_MEMORY exactly like a full device: the knob a host uses to share a GPU, and what the tests use to

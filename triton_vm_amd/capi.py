@@ -316,6 +316,11 @@ class Context:
         """TVM_OPTION_AIR_CHECK_CHUNK_ROWS: rows per chunk of check_constraints (a power of two in 16 .. 2^20; 0: the default, 2^18)"""
         self._check(self.lib.tvm_ctx_set_option(self.handle, 9, rows), "tvm_ctx_set_option")
 
+    def segments_from_coefficients(self, on=True):
+        """TVM_OPTION_SEGMENTS_FROM_COEFFICIENTS: the quotient-segment table is extended from the segments' coefficients (the default);
+        off: from their values on the roots of unity (A/B).  The same words either way."""
+        self._check(self.lib.tvm_ctx_set_option(self.handle, 11, 1 if on else 0), "tvm_ctx_set_option")
+
     def check_constraints(self, d_main_trace, d_aux_trace, n_rows, challenges, seed=None, capacity=1024):
         """tvm_check_constraints: the AIR on the trace itself (initial constraints on row 0, consistency on every row, transition on
         rows r, r + 1, terminal on the last row).  d_main_trace [379][n_rows] / d_aux_trace [91][n_rows][3] words on the device

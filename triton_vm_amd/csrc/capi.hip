@@ -674,10 +674,20 @@ static int quotient_segments_of_coefficients(tvm_ctx* c, const u64* coeffs, u64 
     }
     const u64 X = L / M;
     const bool via_lde = M >= 16 && X >= 2;   // the table kernels' shapes (ntt.hip: lde_table)
+    // The polynomials are zero from `len` on (k_randomized_segments): a quarter of the quotient's coefficients, or the randomizer's.
+    // With n the largest power of two in len (at least 16) and h = len - n <= n more, lo + X^n hi = (lo + hi) + (X^n - 1) hi is an
+    // n-coefficient interpolant plus zerofier times randomizer -- the shape lde_table extends, and it reads the coefficients directly
+    // (LdeSplit mode 2: no transform onto the roots of unity and back).  At 2^20 rows len = 2^20 + 256 where poly_len is 2^21.
+    u64 len = (n_coeffs + 3) / 4 > n_rand ? (n_coeffs + 3) / 4 : n_rand;
+    if (len > poly_len) len = poly_len;
+    u64 n = 16;
+    while (2 * n <= len) n <<= 1;
+    const u64 h = len > n ? len - n : 0;
+    const bool from_coeffs = c->segments_from_coefficients && polys_in == d_polys && 2 * n <= L && L / n <= 32 /* ntt.hip: TVM_LDE_MAX_COSETS */;
     tvm_table* t = new (std::nothrow) tvm_table();
     if (!t) return set_error(c, TVM_ERR_OUT_OF_MEMORY, "table handle");
     t->rows = L;
-    t->layout = via_lde ? lde_table_layout(M, L) : tab_layout_natural(L);
+    t->layout = from_coeffs ? lde_table_layout(n, L) : via_lde ? lde_table_layout(M, L) : tab_layout_natural(L);
     t->n_cols = 5;
     t->fk = 3;
     t->W = 15;
@@ -687,7 +697,20 @@ static int quotient_segments_of_coefficients(tvm_ctx* c, const u64* coeffs, u64 
         return set_error(c, TVM_ERR_OUT_OF_MEMORY, "segment table allocation");
     }
     int rc = TVM_OK;
-    if (via_lde) {
+    if (from_coeffs) {
+        // one pass over the coefficients into the order pass 2 reads them in, the hi part behind it as the randomizers; then the
+        // forward half of the extension (d_polys stays as it is: the out-of-domain evaluations read it)
+        u64* form = (u64*)scratch(c, Scratch::SegmentValues, (size_t)15 * (n + h) * sizeof(u64));
+        if (!form) rc = set_error(c, TVM_ERR_OUT_OF_MEMORY, "segment coefficient form scratch");
+        u64* rnd = h ? form + 15 * n : nullptr;
+        if (rc == TVM_OK) rc = lde_coefficient_form(c, d_polys, len, 3, 3 * poly_len, 15, 3, n, h, form, rnd);
+        if (rc == TVM_OK && t->layout.storage_rows() % TVM_RB) {
+            const u64 full = t->layout.storage_rows() / TVM_RB * TVM_RB * (u64)t->W;
+            (void)hipMemsetAsync(t->data + full, 0, t->bytes() - full * sizeof(u64), c->stream);
+        }
+        const LdeSplit split{2, form, 0, 15};
+        if (rc == TVM_OK) rc = lde_table(c, 3, nullptr, n, 5, rnd, h, bfe_pow(ldt.generator, L / n), ldt.offset, ldt.generator, L, t->data, 0, &split);
+    } else if (via_lde) {
         // The 5 polynomials have fewer than M coefficients: their values on the M-th roots of unity (one transform of 15
         // base-field columns) are a "trace" whose low-degree extension onto the LDT domain is the segment table -- the table
         // kernels write it coset-major and row-block-major directly (context.h), at a quarter of the cost per column of X

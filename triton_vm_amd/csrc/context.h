@@ -124,7 +124,8 @@ enum class Scratch : int {
     // ---- helper slots
     FoldedCoefficients,     // tvm_evaluate: more coefficients than points, reduced modulo X^L - offset^L
     SegmentFolded,          // quotient_segments_of_coefficients: the same reduction of the five segment polynomials
-    SegmentValues,          // ... and their values, on the M-th roots of unity or (short domains) as planar codewords
+    SegmentValues,          // ... and their coefficient form with the randomizers behind it (lde_coefficient_form), or -- the route
+                            // through the values -- their values on the M-th roots of unity or (short domains) as planar codewords
     // ---- entry-point slots
     GatherIndices,          // tvm_table_reveal_rows, tvm_gather_elements(_batch): the indices ...
     GatherOut,              // ... and what they select, on its way to the host
@@ -179,7 +180,8 @@ struct tvm_ctx {
     int lde_chunk_columns = 0;                          // TVM_OPTION_LDE_CHUNK_COLUMNS: 0 = chosen by lde_table (ntt.hip)
     int lde_pass2_tiles = 0;                            // TVM_OPTION_LDE_PASS2_TILES: 1 = the tile kernels instead of k_lde_pass2_fused (A/B)
     u64 lde_pass1_workgroups = 0;                       // TVM_OPTION_LDE_PASS1_WORKGROUPS: 0 = one per (column, tile) item (lde_plan.h)
-    u64 merkle_min_workgroups = 4096;                   // TVM_OPTION_MERKLE_MIN_WORKGROUPS (hash.hip: merkle_tree_from_leaves)
+    bool segments_from_coefficients = true;             // TVM_OPTION_SEGMENTS_FROM_COEFFICIENTS (capi.hip: quotient_segments_of_coefficients)
+    u64 merkle_min_workgroups = 4096;                  // TVM_OPTION_MERKLE_MIN_WORKGROUPS (hash.hip: merkle_tree_from_leaves)
     bool merkle_subtrees = true;                        // TVM_OPTION_MERKLE_SUBTREES: narrow levels seven to a launch (k_merkle_subtrees)
     std::string last_error;
     hipEvent_t ev_start = nullptr, ev_stop = nullptr;

@@ -369,6 +369,10 @@ int32_t tvm_ctx_set_option(tvm_ctx* c, int32_t option, uint64_t value) {
         c->air_check_chunk_rows = value ? value : 1ull << 18;
         return TVM_OK;
     }
+    if (option == TVM_OPTION_SEGMENTS_FROM_COEFFICIENTS) {
+        c->segments_from_coefficients = value != 0;
+        return TVM_OK;
+    }
     if (option == TVM_OPTION_MERKLE_MIN_WORKGROUPS) {
         c->merkle_min_workgroups = value ? value : 4096;
         return TVM_OK;

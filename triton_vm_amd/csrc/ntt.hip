@@ -1405,6 +1405,101 @@ int ntt_columns(tvm_ctx* c, const u64* in, u64 in_len, int in_fk, u64 in_col_str
     return TVM_OK;
 }
 
+// ------------------------------------------------------------------------------------------------
+// Natural-order coefficients -> the library's COEFFICIENT FORM (LdePass2Args::mode), so that a polynomial that is already known by
+// its coefficients enters lde_table behind the inverse transforms (TVM_LDE_FORWARD_ONLY).  A polynomial lo + X^N hi of N + h
+// coefficients, h <= N, is (lo + hi) + (X^N - 1) hi: the N-coefficient interpolant lo + hi and the randomizer hi of pass 2.
+//   in:  element i of virtual column v at in[(v / in_fk) * in_col_stride + i * in_fk + v % in_fk], zero from in_len on (in_len <= N + h)
+//   y:   [v][position p][position q] = N * (lo + hi)[brev(q) * n1 + brev(p)] -- what TVM_LDE_INVERSE_ONLY leaves there
+//   rnd: [v / fk][h][fk] = hi
+struct LdeCoefficientFormArgs {
+    const u64* in;
+    u64 in_len, in_col_stride, h;
+    int in_fk, fk;
+    int log_n1, log_n2;
+    u64 n_mont;   // N
+    u64* y;
+    u64* rnd;
+};
+// One word per work-item, any shape: the axes of short traces, and columns that do not come in whole groups of in_fk.
+__global__ void __launch_bounds__(256) k_lde_coefficient_form(LdeCoefficientFormArgs a) {
+    const u64 n = 1ull << (a.log_n1 + a.log_n2);
+    const u64 o = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (o >= n) return;
+    const int v = blockIdx.y;
+    const u64 p = o >> a.log_n2, q = o & ((1ull << a.log_n2) - 1);
+    const u64 m = ((u64)brev_bits((u32)q, a.log_n2) << a.log_n1) + brev_bits((u32)p, a.log_n1);
+    const u64* in = a.in + (u64)(v / a.in_fk) * a.in_col_stride + (v % a.in_fk);
+    u64 x = m < a.in_len ? in[m * a.in_fk] : 0;
+    if (m < a.h) {
+        const u64 r = n + m < a.in_len ? in[(n + m) * a.in_fk] : 0;
+        x = bfe_add(x, r);
+        a.rnd[((u64)(v / a.fk) * a.h + m) * a.fk + v % a.fk] = r;
+    }
+    a.y[(u64)v * n + o] = bfe_mul(x, a.n_mont);
+}
+// Axes of 16 points and more, columns in groups of in_fk (one polynomial over the extension field, array-of-structures): a workgroup
+// takes the 16 x 16 coefficients m1 = m1_lo + j * n2/16, m2 = m2_0 + i of one group -- 16 runs of 16 * in_fk consecutive words in,
+// and, through LDS, 16 * in_fk runs of 16 consecutive positions q (the high bits of m1 are the low bits of q) out: full lines both ways.
+__global__ void __launch_bounds__(256) k_lde_coefficient_form_tiles(LdeCoefficientFormArgs a) {
+    constexpr int RS = 16 * 3 + 1;
+    __shared__ u64 s[16 * RS];
+    const int tid = threadIdx.x;
+    const u64 n2 = 1ull << a.log_n2, n = n2 << a.log_n1;
+    const u64 tiles_m2 = 1ull << (a.log_n1 - 4);
+    const u64 m2_0 = ((u64)blockIdx.x & (tiles_m2 - 1)) << 4, m1_lo = (u64)blockIdx.x >> (a.log_n1 - 4);
+    const int g = blockIdx.y;
+    const int run = 16 * a.in_fk;
+    const u64* in = a.in + (u64)g * a.in_col_stride;
+    for (int idx = tid; idx < 16 * run; idx += 256) {
+        const int j = idx / run, w = idx % run;
+        const u64 m = ((m1_lo + ((u64)j << (a.log_n2 - 4))) << a.log_n1) + m2_0 + (u64)(w / a.in_fk);
+        const int comp = w % a.in_fk;
+        u64 x = m < a.in_len ? TVM_LOAD_STREAM(&in[m * a.in_fk + comp]) : 0;
+        if (m < a.h) {  // few workgroups
+            const u64 r = n + m < a.in_len ? in[(n + m) * a.in_fk + comp] : 0;
+            x = bfe_add(x, r);
+            const int v = g * a.in_fk + comp;
+            a.rnd[((u64)(v / a.fk) * a.h + m) * a.fk + v % a.fk] = r;
+        }
+        s[j * RS + w] = bfe_mul(x, a.n_mont);
+    }
+    tvm_lds_barrier();
+    for (int idx = tid; idx < 16 * run; idx += 256) {
+        const int q_lo = idx & 15, i = (idx >> 4) & 15, comp = idx >> 8;
+        const int j = (int)brev_bits((u32)q_lo, 4);
+        const u64 q = brev_bits((u32)(m1_lo + ((u64)j << (a.log_n2 - 4))), a.log_n2);
+        const u64 p = brev_bits((u32)(m2_0 + (u64)i), a.log_n1);
+        a.y[(u64)(g * a.in_fk + comp) * n + p * n2 + q] = s[j * RS + i * a.in_fk + comp];
+    }
+}
+
+int lde_coefficient_form(tvm_ctx* c, const u64* in, u64 in_len, int in_fk, u64 in_col_stride, int ncols, int fk, u64 n_rows, u64 h,
+                         u64* coeffs, u64* rnd) {
+    if (!is_pow2(n_rows) || n_rows < 2 || n_rows > (1ull << 24) || h > n_rows || in_len > n_rows + h || (in_fk != 1 && in_fk != 3) ||
+        (fk != 1 && fk != 3) || ncols <= 0 || ncols >= 65536 || ncols % fk || !in || !coeffs || (h && !rnd))
+        return set_error(c, TVM_ERR_INVALID_ARGUMENT, "lde_coefficient_form arguments");
+    const Split sp = split_for(n_rows);
+    LdeCoefficientFormArgs a;
+    a.in = in;
+    a.in_len = in_len;
+    a.in_col_stride = in_col_stride;
+    a.h = h;
+    a.in_fk = in_fk;
+    a.fk = fk;
+    a.log_n1 = sp.log_n1;
+    a.log_n2 = sp.log_n2;
+    a.n_mont = bfe_from_u64(n_rows);
+    a.y = coeffs;
+    a.rnd = rnd;
+    if (sp.log_n1 >= 4 && ncols % in_fk == 0)   // (log_n2 >= log_n1)
+        TVM_LAUNCH(k_lde_coefficient_form_tiles, dim3((unsigned)(n_rows >> 8), (unsigned)(ncols / in_fk)), dim3(256), 0, c->stream, a);
+    else
+        TVM_LAUNCH(k_lde_coefficient_form, dim3((unsigned)((n_rows + 255) / 256), (unsigned)ncols), dim3(256), 0, c->stream, a);
+    TVM_HIP_CHECK(c, hipGetLastError());
+    return TVM_OK;
+}
+
 // Columns per chunk of lde_table (chunk_cols <= 0: the caller leaves the choice to the context's option, and that to this policy).
 // range_cols: the virtual columns this call transforms.
 static int lde_chunk_columns(tvm_ctx* c, int chunk_cols, u64 X, u64 n_rows, int W, int range_cols, bool split) {
