@@ -114,6 +114,13 @@ int32_t tvm_ctx_trim(tvm_ctx* ctx);
  * length max(n_coeffs / 4, n_rand), the coefficients beyond n are the randomizer part of the extension.  0: the segments' values on
  * the roots of unity first and the whole extension from there (A/B).  The same words either way. */
 #define TVM_OPTION_SEGMENTS_FROM_COEFFICIENTS 11
+/* TVM_OPTION_LDE_PASS2_SCALE_ABSORBED (default 0): the middle pass of tvm_lde_table on 256- to 2048-point axes (k_lde_pass2_fused) does
+ * not multiply its coefficients by the coset's factors in every coset.  The part of the factor that is common to a lane's first
+ * butterfly group moves into the next group's twiddle table, the rest is a power of two per coset -- the first group at shifted points,
+ * the same instructions -- times a factor per class of cosets that the coefficients take once per class: 48 general multiplications
+ * per lane and coset instead of 63.  Taken where the evaluation generator is the domains' own root of unity of order L (every
+ * ArithmeticDomain's is; any offset); other generators run the table form whatever the value.  The same words either way. */
+#define TVM_OPTION_LDE_PASS2_SCALE_ABSORBED 12
 int32_t tvm_ctx_set_option(tvm_ctx* ctx, int32_t option, uint64_t value);
 /* Cap on the bytes this context may hold through tvm_malloc / table handles (0 = no cap).  Requests beyond it fail
  * with TVM_ERR_OUT_OF_MEMORY exactly like a full device: the knob a host uses to share a GPU, and what the tests use to

@@ -321,6 +321,11 @@ class Context:
         off: from their values on the roots of unity (A/B).  The same words either way."""
         self._check(self.lib.tvm_ctx_set_option(self.handle, 11, 1 if on else 0), "tvm_ctx_set_option")
 
+    def lde_pass2_scale_absorbed(self, on=True):
+        """TVM_OPTION_LDE_PASS2_SCALE_ABSORBED: the middle pass of the table extension folds the coset scale into its butterflies and
+        twiddle tables instead of multiplying by it in every coset (A/B).  The same words either way."""
+        self._check(self.lib.tvm_ctx_set_option(self.handle, 12, 1 if on else 0), "tvm_ctx_set_option")
+
     def check_constraints(self, d_main_trace, d_aux_trace, n_rows, challenges, seed=None, capacity=1024):
         """tvm_check_constraints: the AIR on the trace itself (initial constraints on row 0, consistency on every row, transition on
         rows r, r + 1, terminal on the last row).  d_main_trace [379][n_rows] / d_aux_trace [91][n_rows][3] words on the device

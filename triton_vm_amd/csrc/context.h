@@ -158,7 +158,8 @@ enum class Scratch : int {
 //   Pass2Twiddles      (trace generator, n1, n2): f of k_lde_pass2_fused                                       ntt.hip: pass2_fused_tables
 //   Pass2CosetFactors  (offset, generator, X << 56 | n1 << 28 | n2): hi_pos and u of k_lde_pass2_fused
 //   Pass3Halves        (root of the n1-point axis, 2048, 0): the twiddles of k_lde_pass3_halves                ntt.hip: lde_table
-enum class TableKind { Powers, CosetFactors, Pass2Twiddles, Pass2CosetFactors, Pass3Halves };
+//   Pass2ScaleAbsorbed (offset, generator, X << 56 | n1 << 28 | n2): g_abs and d_abs of k_lde_pass2_fused      ntt.hip: pass2_absorbed_tables
+enum class TableKind { Powers, CosetFactors, Pass2Twiddles, Pass2CosetFactors, Pass3Halves, Pass2ScaleAbsorbed };
 }  // namespace tvm
 
 struct tvm_ctx {
@@ -179,7 +180,8 @@ struct tvm_ctx {
     bool air_valid_trace = false;                       // TVM_OPTION_AIR_VALID_TRACE (capi.hip: tvm_all_quotients_combined)
     int lde_chunk_columns = 0;                          // TVM_OPTION_LDE_CHUNK_COLUMNS: 0 = chosen by lde_table (ntt.hip)
     int lde_pass2_tiles = 0;                            // TVM_OPTION_LDE_PASS2_TILES: 1 = the tile kernels instead of k_lde_pass2_fused (A/B)
-    u64 lde_pass1_workgroups = 0;                       // TVM_OPTION_LDE_PASS1_WORKGROUPS: 0 = one per (column, tile) item (lde_plan.h)
+    bool lde_pass2_scale_absorbed = false;              // TVM_OPTION_LDE_PASS2_SCALE_ABSORBED (ntt.hip: lde_table, k_lde_pass2_fused)
+    u64 lde_pass1_workgroups = 0;                      // TVM_OPTION_LDE_PASS1_WORKGROUPS: 0 = one per (column, tile) item (lde_plan.h)
     bool segments_from_coefficients = true;             // TVM_OPTION_SEGMENTS_FROM_COEFFICIENTS (capi.hip: quotient_segments_of_coefficients)
     u64 merkle_min_workgroups = 4096;                  // TVM_OPTION_MERKLE_MIN_WORKGROUPS (hash.hip: merkle_tree_from_leaves)
     bool merkle_subtrees = true;                        // TVM_OPTION_MERKLE_SUBTREES: narrow levels seven to a launch (k_merkle_subtrees)

@@ -342,6 +342,10 @@ int32_t tvm_ctx_set_option(tvm_ctx* c, int32_t option, uint64_t value) {
         c->lde_pass2_tiles = value ? 1 : 0;
         return TVM_OK;
     }
+    if (option == TVM_OPTION_LDE_PASS2_SCALE_ABSORBED) {
+        c->lde_pass2_scale_absorbed = value != 0;
+        return TVM_OK;
+    }
     if (option == TVM_OPTION_LDE_PASS1_WORKGROUPS) {
         if (value > (1ull << 30)) return set_error(c, TVM_ERR_INVALID_ARGUMENT, "TVM_OPTION_LDE_PASS1_WORKGROUPS: at most 2^30");
         c->lde_pass1_workgroups = value;

@@ -27,6 +27,7 @@
 // The LDS-resident transforms run at their VGPR budgets (128 at 4 wavefronts per SIMD): the carry-out form of bfe_mul
 // (field.h) keeps one more register pair live per product and measured 3-7 % slower in the three passes.
 #define TVM_MUL_CARRY_FORM 0
+#include <type_traits>
 #include <cstdlib>
 #include <cstring>
 
@@ -383,6 +384,10 @@ struct LdePass2Args {
     const u64* g_hi_pos; // [X][N2]: gamma_k^(N1*brev(q)) at POSITION q of a row (g_hi in the order the row holds its coefficients)
     const u64* f_tw;     // [N1 rows p][64 lanes][4 it][4 e]: w_N2^(g brev2(e)) * w_N^(brev(p) g), g = lane + 64 it (a lane's 16 values: one line)
     const u64* u_tw;     // [X][N1 rows p][4]: (gamma_k^m2 / N) * w_N^(m2 * 256 e), m2 = brev(p)
+    // ... with the coset scale absorbed (TVM_OPTION_LDE_PASS2_SCALE_ABSORBED; the comment above k_lde_pass2_fused):
+    int scale_absorbed;  // 1: the coset loop takes the two tables below instead of g_hi_pos (lde_table decides it per call)
+    const u64* g_abs;    // [X][N2]: gamma_k^(N1*brev(q >> 4)) * w_N2^(((q & 15) brev4((q >> 4) & 15)) << (LOGN - 8)) at position q
+    const u64* d_abs;    // [max(1, X/4) classes][16]: (class 0: offset^(N/16), then: generator^(N/16)) ^ brev4(e)
 };
 
 __global__ void __launch_bounds__(1024) k_lde_pass2(LdePass2Args a) {
@@ -994,6 +999,31 @@ __global__ void __launch_bounds__((1 << (LOGN - 4)) * ROWS, 4) k_lde_pass1_rows(
 // 344 B of scratch, 2.4 times the time per cell -- or, at 256 points, the 64-work-item stand-in k_lde_pass2_v3<8, 6>): 32 / 16 lanes
 // per row, TWO / FOUR rows per wavefront (everything between two butterfly groups of a row stays inside its wavefront, as at 1024
 // points), the last group radix 2 / nothing but the inter-pass factors; 256 / 128 work-items, 42 / 23 KB of LDS.
+//
+// The coset scale absorbed (a.scale_absorbed, TVM_OPTION_LDE_PASS2_SCALE_ABSORBED; lde_table sets it when the evaluation generator is
+// the domains' own root of order X N): the 16 multiplications x[e] = coef[e] * gamma_k^(n1 m1) per lane and coset are not issued.
+// Position 16 rl + e holds coefficient m1 = a n2/16 + r, a = brev4(e), r = brev(rl), so the factor is gamma_k^(n1 r) * (gamma_k^(N/16))^a.
+//   * gamma_k^(N/16) = offset^(N/16) * w_16X^k, and the domains' roots of order <= 64 are powers of two (ntt_shift.h).  The cosets are
+//     walked as k = rho + s kappa, s = max(1, X/4) classes rho of min(X, 4) cosets: w_16X^(s kappa) = 2^(U kappa), U = 39 (X >= 4) or
+//     78 (X = 2).  (gamma_k^(N/16))^a = D_rho^a * 2^(U kappa a) with D_rho = offset^(N/16) w_16X^rho.
+//   * D_rho^a does not depend on kappa: coef[] is multiplied by it once per class (d_abs: 15 multiplications by uniform factors, from
+//     one class to the next by w_16X^a) -- 15 s multiplications per lane and row where the loop spent 16 X.
+//   * 2^(U kappa a) on the inputs of the first group is that group at shifted points (ntt_pow2_points_shifted): the same butterflies
+//     with other shift counts, one instantiation per kappa behind a uniform branch.
+//   * gamma_k^(n1 r) is common to the lane's 16 outputs of the first group and meets the middle group's twiddle step, which multiplied 15
+//     of its 16 inputs already: g_abs holds the product per position, staged a coset ahead in the words g_hi_pos had (ghl), and the
+//     middle group multiplies all 16 inputs by it; the compact table tw2 is not read in the loop.
+//   * Position 0 of row-lane 0 (the randomizer term) has every factor equal to 1, as before.
+// 48 general multiplications per lane and coset instead of 63 and 15 LDS reads fewer; Z is addressed by k, so the order of the cosets is
+// free.  The same words either way.  What it does not save: with kappa != 0 none of the first group's 32 butterflies has the twiddle 1
+// (15 of them have in the table form and at kappa = 0), so three cosets out of four issue 15 more shift multiplications of 9 to 12
+// instructions where 16 general ones of 14 went, and the group no longer writes into fresh registers.  Measured: a few
+// per cent of the kernel's instructions at most -- an option for A/B, not the default.  Each form has a coset loop of its own (the form
+// is a constant inside), so the table form's loop is the code it was.  TVM_P2F_ABSORB: the instantiations (bit LOGN) that contain this form at all -- not the 2048-point
+// one: with the second loop it spills 44 bytes per lane where the table form alone spills 36.
+#ifndef TVM_P2F_ABSORB
+#define TVM_P2F_ABSORB ((1 << 8) | (1 << 9) | (1 << 10))
+#endif
 template <int LOGN>
 // (below 1024 points the LDS leaves room for three wavefronts per SIMD: the register budget is set for three, and nothing spills)
 __global__ void __launch_bounds__(8 << (LOGN - 4), LOGN >= 10 ? 4 : 3) k_lde_pass2_fused(LdePass2Args a) {
@@ -1041,8 +1071,11 @@ __global__ void __launch_bounds__(8 << (LOGN - 4), LOGN >= 10 ? 4 : 3) k_lde_pas
         for (int e = 0; e < 16; e++) rowl[LSTEP * e] = TVM_LOAD_STREAM(&y[LPR * e]);   // position rl + LPR e
     }
     for (int i = tid; i < 256; i += NT) tw2[17 * (i >> 4) + (i & 15)] = a.tw_b1[((i >> 4) * brev_bits((u32)(i & 15), 4)) << (LOGN - 8)];
+    // (uniform: which form of the coset loop this launch takes, and the table of per-position factors that goes with it)
+    const bool absorbed = ((TVM_P2F_ABSORB >> LOGN) & 1) && a.scale_absorbed;
+    const u64* const gtab = absorbed ? a.g_abs : a.g_hi_pos;
 #pragma unroll
-    for (int hh = 0; hh < n2 / NT; hh++) ghl[TVM_ROW_SKEW(tid + hh * NT)] = a.g_hi_pos[tid + hh * NT];
+    for (int hh = 0; hh < n2 / NT; hh++) ghl[TVM_ROW_SKEW(tid + hh * NT)] = gtab[tid + hh * NT];   // (either walk starts at coset 0)
     if constexpr (WPR <= 1) tvm_wave_sync();
     else tvm_lds_barrier();   // (the row is loaded, the pair flags are zero)
     // inverse rows step: position q of the row then holds N * t[m1*n1 + m2], m1 = brev(q), m2 = brev(p)
@@ -1065,18 +1098,39 @@ __global__ void __launch_bounds__(8 << (LOGN - 4), LOGN >= 10 ? 4 : 3) k_lde_pas
     u64* const r0 = ghl + TVM_ROW_WORDS(n2) + r;
     if (rl == 0) *r0 = has_rnd ? a.rnd[((u64)(v / a.fk) * a.h + m2) * a.fk + (v % a.fk)] : 0;
     tvm_lds_barrier();   // the twiddle tables and the first coset's factors are staged
-    for (int k = 0; k < a.n_cosets; k++) {
+    // the walk of the absorbed form: step = rho * 2^log_nk + kappa -> coset k = rho + kappa * classes (all uniform)
+    const int log_nk = a.n_cosets >= 4 ? 2 : a.n_cosets >> 1, classes = a.n_cosets >> log_nk;
+    // (the loop once per form, the form a constant inside: the table form's loop is the one this kernel had before the other arrived)
+    const auto coset_loop = [&](auto form) {
+    constexpr bool ABS = decltype(form)::value;
+    const auto coset_of = [&](int step) { return ABS ? (step >> log_nk) + (step & ((1 << log_nk) - 1)) * classes : step; };
+    for (int step = 0; step < a.n_cosets; step++) {
+        const int k = coset_of(step);
         // (lane and work-item number through opaque moves: the addresses below are cheap to form and expensive to keep -- hoisted out
         // of the coset loop they went to scratch)
         const int ln = tvm_opaque(rl);
+        int shift = 0;   // the first group's points are 2^(39 shift) w_16^j
         u64 x[16];
-        {
+        if constexpr (ABS) {
+            const int kappa = step & ((1 << log_nk) - 1);
+            if (kappa == 0) {   // a new class: coef[e] takes D_rho^a / D_(rho - 1)^a
+                const u64* const d = a.d_abs + 16 * (step >> log_nk);
+#pragma unroll
+                for (int e = 1; e < 16; e++) coef[e] = bfe_mul(coef[e], d[e]);
+            }
+            shift = a.n_cosets == 2 ? 2 * kappa : kappa;
+#pragma unroll
+            for (int e = 0; e < 16; e++) x[e] = coef[e];
+        } else {
             const u64* const gh = ghl + 17 * ln;   // the coset's factors at positions 16 rl + e (staged by the workgroup, below)
 #pragma unroll
             for (int e = 0; e < 16; e++) x[e] = bfe_mul(coef[e], gh[e]);
         }
         if (has_rnd && ln == 0) x[0] = bfe_add(coef[0], bfe_mul(a.zk[k], *r0));   // gamma_k^0 = 1 at position 0
-        ntt_pow2_points<4, true, false>(x);
+        if (!ABS || shift == 0) ntt_pow2_points<4, true, false>(x);
+        else if (shift == 1) ntt_pow2_points_shifted<4, 39>(x);
+        else if (shift == 2) ntt_pow2_points_shifted<4, 78>(x);
+        else ntt_pow2_points_shifted<4, 117>(x);
         {
             u64* const out = row + 17 * ln;
 #pragma unroll
@@ -1094,10 +1148,19 @@ __global__ void __launch_bounds__(8 << (LOGN - 4), LOGN >= 10 ? 4 : 3) k_lde_pas
             u64 x2[16];
 #pragma unroll
             for (int e = 0; e < 16; e++) x2[e] = q[17 * e];
+            if constexpr (ABS) {   // the twiddle step times the first group's gamma_k^(n1 r), per position (g_abs, staged below)
+                const u64* const g = ghl + TVM_ROW_SKEW(((ln >> 4) << 8) | j0);
 #pragma unroll
-            for (int e = 1; e < 16; e++) {
-                x2[e] = bfe_mul(x2[e], t2[e]);
-                if (e % TVM_P2F_TWB == 0) asm volatile("" ::: "memory");
+                for (int e = 0; e < 16; e++) {
+                    x2[e] = bfe_mul(x2[e], g[17 * e]);
+                    if (e % TVM_P2F_TWB == 0) asm volatile("" ::: "memory");
+                }
+            } else {
+#pragma unroll
+                for (int e = 1; e < 16; e++) {
+                    x2[e] = bfe_mul(x2[e], t2[e]);
+                    if (e % TVM_P2F_TWB == 0) asm volatile("" ::: "memory");
+                }
             }
             ntt_pow2_points<4, true, false>(x2);
 #pragma unroll
@@ -1129,10 +1192,11 @@ __global__ void __launch_bounds__(8 << (LOGN - 4), LOGN >= 10 ? 4 : 3) k_lde_pas
             const int t2 = tvm_opaque(tid), b_out = t2 & (ROWS - 1), j1_0 = t2 >> RLOG;
             // the next coset's factors: requested here, parked in LDS at the end of the store phase (every wavefront has read this
             // coset's before the barrier above) -- their latency hides behind the store phase and costs two registers
-            const bool more = k + 1 < a.n_cosets;
+            const bool more = step + 1 < a.n_cosets;
+            const u64* const gn = gtab + (u64)coset_of(step + 1) * n2;
             u64 g_next[n2 / NT];
 #pragma unroll
-            for (int hh = 0; hh < n2 / NT; hh++) g_next[hh] = more ? a.g_hi_pos[(u64)(k + 1) * n2 + t2 + hh * NT] : 0;
+            for (int hh = 0; hh < n2 / NT; hh++) g_next[hh] = more ? gn[t2 + hh * NT] : 0;
             // a lane copies TWO adjacent rows of a position with one 16-byte store: 8 store instructions per lane and coset instead of
             // 16 for the same 64-byte runs (-3 % of the kernel, profiles/r05_k_*)
             (void)b_out, (void)j1_0;
@@ -1151,18 +1215,35 @@ __global__ void __launch_bounds__(8 << (LOGN - 4), LOGN >= 10 ? 4 : 3) k_lde_pas
         }
         tvm_lds_barrier();   // the tile has been read: the next coset's first group overwrites the rows
     }
+    };
+    if constexpr ((TVM_P2F_ABSORB >> LOGN) & 1) {
+        if (absorbed) return coset_loop(std::true_type{});
+    }
+    coset_loop(std::false_type{});
 }
 
 // the tables of k_lde_pass2_fused (LdePass2Args), for rows of n2 = 1024 or 2048 points: LPR = n2 / 16 lanes per row, the last
 // butterfly group of radix R3 = n2 / 256 in 16 / R3 iterations.  hi_pos[k][q] = hi[k][brev(q)];
 // f[((p*LPR + rl)*16 + it*R3 + e] = tw_n2[g * brev(e)] * w_N^(brev(p) * g), g = rl + LPR it;
 // u[(k*n1 + p)*R3 + e] = lo[k][brev(p)] * w_N^(brev(p) * 256 e)
+// The scale-absorbed form's tables (g_abs null: not asked for): g_abs[k][q] = hi[k][brev(q >> 4)] * tw_n2[((q & 15) brev4((q >> 4) & 15))
+// << (log_n2 - 8)]; d_abs[16 rho + e] = (rho == 0 ? d_first : d_step)^brev4(e), d_first = offset^(N/16), d_step = generator^(N/16).
 __global__ void k_pass2_fused_tables(const u64* __restrict__ lo, const u64* __restrict__ hi, Pow2 tw_inter, const u64* __restrict__ tw_n2,
-                                     int log_n1, int log_n2, u64 X, u64* __restrict__ hi_pos, u64* __restrict__ f, u64* __restrict__ u) {
+                                     int log_n1, int log_n2, u64 X, u64* __restrict__ hi_pos, u64* __restrict__ f, u64* __restrict__ u,
+                                     u64* __restrict__ g_abs, u64* __restrict__ d_abs, u64 d_first, u64 d_step) {
     const u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
     const u64 n1 = 1ull << log_n1, n2 = 1ull << log_n2, n = n1 * n2;
     const int k3 = log_n2 - 8;
     const u64 r3 = 1ull << k3, lpr = n2 >> 4;
+    if (g_abs) {
+        if (i < X * n2) {
+            const u64 q = i % n2;
+            g_abs[i] = bfe_mul(hi[(i / n2) * n2 + brev_bits((u32)(q >> 4), log_n2 - 4)],
+                               tw_n2[((q & 15) * (u64)brev_bits((u32)((q >> 4) & 15), 4)) << k3]);
+        }
+        if (i < 16 * (X >= 4 ? X / 4 : 1)) d_abs[i] = bfe_pow(i < 16 ? d_first : d_step, (u64)brev_bits((u32)(i & 15), 4));
+        return;
+    }
     if (i < X * n2) hi_pos[i] = hi[(i / n2) * n2 + brev_bits((u32)(i % n2), log_n2)];
     if (f && i < n) {
         const u64 e = i & (r3 - 1), it = (i >> k3) & ((16 >> k3) - 1), rl = (i >> 4) & (lpr - 1), p = i >> log_n2, g = rl + lpr * it;
@@ -1281,11 +1362,27 @@ static int pass2_fused_tables(tvm_ctx* c, u64 trace_gen, u64 offset, u64 gen, u6
         const u64 total = new_f ? (n > X * (n2 + r3 * n1) ? n : X * (n2 + r3 * n1)) : X * (n2 > r3 * n1 ? n2 : r3 * n1);
         // (entries that exist already are simply written again with the same values when only one of the two is new)
         TVM_LAUNCH(k_pass2_fused_tables, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, c->stream, lo, hi, tw_inter, tw_n2, log_n1,
-                   log_n2, X, d_k, new_f ? d_f : (u64*)nullptr, d_k + X * n2);
+                   log_n2, X, d_k, new_f ? d_f : (u64*)nullptr, d_k + X * n2, (u64*)nullptr, (u64*)nullptr, (u64)0, (u64)0);
     }
     *f = d_f;
     *hi_pos = d_k;
     *u = d_k + X * n2;
+    return TVM_OK;
+}
+// ... and the two of its scale-absorbed form (LdePass2Args::g_abs, d_abs), under a key of their own: a context that switches
+// TVM_OPTION_LDE_PASS2_SCALE_ABSORBED never reads the other form's table
+static int pass2_absorbed_tables(tvm_ctx* c, u64 offset, u64 gen, u64 X, int log_n1, int log_n2, const u64* lo, const u64* hi,
+                                 const Pow2& tw_inter, const u64* tw_n2, const u64** g_abs, const u64** d_abs) {
+    const u64 n1 = 1ull << log_n1, n2 = 1ull << log_n2, n = n1 * n2, classes = X >= 4 ? X / 4 : 1;
+    if (!bind_device(c)) return set_error(c, TVM_ERR_DEVICE, "bind device");
+    bool is_new = false;
+    u64* d = cached_table(c, TableKind::Pass2ScaleAbsorbed, offset, gen, (X << 56) | (n1 << 28) | n2, X * n2 + 16 * classes, &is_new);
+    if (!d) return set_error(c, TVM_ERR_OUT_OF_MEMORY, "pass-2 scale-absorbed tables");
+    if (is_new)   // (X n2 >= 256 > 16 classes entries)
+        TVM_LAUNCH(k_pass2_fused_tables, dim3((unsigned)((X * n2 + 255) / 256)), dim3(256), 0, c->stream, lo, hi, tw_inter, tw_n2, log_n1, log_n2,
+                   X, (u64*)nullptr, (u64*)nullptr, (u64*)nullptr, d, d + X * n2, bfe_pow(offset, n / 16), bfe_pow(gen, n / 16));
+    *g_abs = d;
+    *d_abs = d + X * n2;
     return TVM_OK;
 }
 
@@ -1583,6 +1680,20 @@ int lde_table(tvm_ctx* c, int fk, const u64* trace, u64 n_rows, u64 n_cols, cons
     if (is_pass2_fused(plan.pass2.kernel))
         TVM_TRY(pass2_fused_tables(c, w, eval_offset, eval_gen, X, sp.log_n1, sp.log_n2, p2.g_lo, p2.g_hi, p2.tw_inter, p2.tw_b1, &p2.g_hi_pos,
                                    &p2.f_tw, &p2.u_tw));
+    // The coset scale absorbed into the butterflies (k_lde_pass2_fused): from one coset of a class to the next, gamma_k^(N/16) must grow
+    // by the power of two the kernel's shifted transforms are built for -- generator^(s N/16) = 2^39 (w_64; s = X/4 classes, X >= 4) or
+    // 2^78 (w_32; X = 2).  The domains' own root of order X N does that (any offset; X <= 32 above), and so does every generator the
+    // checks above let through beside a trace generator that is the domains' own (classify_root; the fused kernel runs for no other)
+    // once 16 X divides N; the test is on the power itself, so whatever else arrives takes the table form of the scale.
+    p2.scale_absorbed = 0;
+    p2.g_abs = p2.d_abs = nullptr;
+    const u64 scale_step = X >= 4 ? bfe_pow(eval_gen, (N / 16) * (X / 4)) : bfe_pow(eval_gen, N / 16);
+    const bool scale_is_shift = X == 1 || scale_step == bfe_pow(bfe_from_u64(2), X >= 4 ? 39 : 78);
+    if (c->lde_pass2_scale_absorbed && is_pass2_fused(plan.pass2.kernel) && mode != TVM_LDE_INVERSE_ONLY && std_roots && N >= 16 && scale_is_shift) {
+        TVM_TRY(pass2_absorbed_tables(c, eval_offset, eval_gen, X, sp.log_n1, sp.log_n2, p2.g_lo, p2.g_hi, p2.tw_inter, p2.tw_b1, &p2.g_abs,
+                                      &p2.d_abs));
+        p2.scale_absorbed = 1;
+    }
     const u64 n_mont = bfe_from_u64(N);
     for (u64 k = 0; k < X; k++) {
         const u64 gamma = bfe_mul(eval_offset, bfe_pow(eval_gen, k));

@@ -85,27 +85,37 @@ struct Pow2Root {
 // In-register transform of 2^K points with the domain's 2^K-th root (INVERSE: its inverse), element e at x[e * STRIDE].
 // DIT: bit-reversed order in, natural order out; DIF: natural order in, bit-reversed order out -- the conventions of
 // lds_ntt_group (ntt.hip), of which these are the twiddle-free lowest / highest layers.
-template <int K, bool DIT, bool INVERSE, int T, int M, int Qi>
+// SHIFT (decimation in time only): the transform at the points 2^SHIFT w^j instead of w^j, which is the plain transform of the
+// inputs c_a 2^(SHIFT a), a = brev(e) the coefficient index at element e.  Layer T joins two transforms of h = 2^T points each
+// in the variable y = x^(R / 2h); its twiddle at the shifted points is (2^SHIFT w^M')^(R / 2h) -- the plain twiddle times
+// 2^(SHIFT (R/2 >> T)), still a power of two: the same instructions with other shift counts.
+template <int K, bool DIT, bool INVERSE, int T, int M, int Qi, int SHIFT = 0>
 struct Ntt2kStep {
     template <typename X>
     TVM_HD static void run(X& x) {
         constexpr int R = 1 << K, h = 1 << T;
+        static_assert(SHIFT == 0 || DIT, "input shift: decimation in time only");
         if constexpr (Qi < R / (2 * h)) {
             constexpr int e = Qi * 2 * h + M;
-            constexpr int E = (Pow2Root<K, INVERSE>::value * M * ((R / 2) >> T)) % 192;
+            constexpr int E = ((Pow2Root<K, INVERSE>::value * M + SHIFT % 192 + 192) * ((R / 2) >> T)) % 192;
             if constexpr (DIT) bfe_butterfly_pow2<E>(x[e], x[e + h]);
             else bfe_butterfly_dif_pow2<E>(x[e], x[e + h]);
-            Ntt2kStep<K, DIT, INVERSE, T, M, Qi + 1>::run(x);
+            Ntt2kStep<K, DIT, INVERSE, T, M, Qi + 1, SHIFT>::run(x);
         } else if constexpr (M + 1 < h) {
-            Ntt2kStep<K, DIT, INVERSE, T, M + 1, 0>::run(x);
+            Ntt2kStep<K, DIT, INVERSE, T, M + 1, 0, SHIFT>::run(x);
         } else if constexpr (DIT ? (T + 1 < K) : (T > 0)) {
-            Ntt2kStep<K, DIT, INVERSE, DIT ? T + 1 : T - 1, 0, 0>::run(x);
+            Ntt2kStep<K, DIT, INVERSE, DIT ? T + 1 : T - 1, 0, 0, SHIFT>::run(x);
         }
     }
 };
 template <int K, bool DIT, bool INVERSE>
 TVM_HD void ntt_pow2_points(u64 (&x)[1 << K]) {
     if constexpr (K > 0) Ntt2kStep<K, DIT, INVERSE, DIT ? 0 : K - 1, 0, 0>::run(x);
+}
+// bit-reversed order in, natural order out: out[j] = sum_a x[brev(a)] (2^SHIFT w^j)^a, w the domains' 2^K-th root
+template <int K, int SHIFT>
+TVM_HD void ntt_pow2_points_shifted(u64 (&x)[1 << K]) {
+    if constexpr (K > 0) Ntt2kStep<K, true, false, 0, 0, 0, SHIFT>::run(x);
 }
 
 }  // namespace tvm
