@@ -87,10 +87,10 @@ int32_t tvm_ctx_trim(tvm_ctx* ctx);
 #define TVM_OPTION_LDE_PASS2_TILES 4
 /* TVM_OPTION_LDE_PASS1_WORKGROUPS: workgroups per launch of the first pass's row kernels on 256-, 512- and 1024-point axes
  * (k_lde_pass1_rows<8 | 9 | 10, 16>), at most one per (column, tile) item of the chunk.  With fewer workgroups than items each walks
- * several tiles with the next tile's input in flight under the current one's butterflies.  0 (default) and any value at or above the
- * item count: one tile per workgroup.  A workgroup per compute unit (256 on an MI355X) makes the kernel 13 % faster at 2^20 rows
- * and a proof 0.4 %, which is inside a proof's run-to-run spread -- hence not the default; the tests use small values
- * to walk many tiles, and the column boundary, in one workgroup. */
+ * several tiles with the next tile's input in flight under the current one's butterflies.  0 and any value at or above the item
+ * count: one tile per workgroup.  A context starts with the compute-unit count of its device (256 on an MI355X: the kernel is 13 %
+ * faster at 2^20 rows than with a workgroup per item), or 0 where the device reports none; the tests use small values to
+ * walk many tiles, and the column boundary, in one workgroup. */
 #define TVM_OPTION_LDE_PASS1_WORKGROUPS 10
 /* TVM_OPTION_AIR_FORK_MAX_WORKGROUPS (default 256; 0 = never): tvm_all_quotients_combined / tvm_air_class_values on a quotient domain of at
  * most this many workgroups of 256 rows launch the parts of the AIR on four streams side by side (the context's and three of its
@@ -114,14 +114,20 @@ int32_t tvm_ctx_trim(tvm_ctx* ctx);
  * length max(n_coeffs / 4, n_rand), the coefficients beyond n are the randomizer part of the extension.  0: the segments' values on
  * the roots of unity first and the whole extension from there (A/B).  The same words either way. */
 #define TVM_OPTION_SEGMENTS_FROM_COEFFICIENTS 11
-/* TVM_OPTION_LDE_PASS2_SCALE_ABSORBED (default 0): the middle pass of tvm_lde_table on 256- to 2048-point axes (k_lde_pass2_fused) does
+/* TVM_OPTION_LDE_PASS2_SCALE_ABSORBED (default 1): the middle pass of tvm_lde_table on 256- to 1024-point axes (k_lde_pass2_fused) does
  * not multiply its coefficients by the coset's factors in every coset.  The part of the factor that is common to a lane's first
  * butterfly group moves into the next group's twiddle table, the rest is a power of two per coset -- the first group at shifted points,
  * the same instructions -- times a factor per class of cosets that the coefficients take once per class: 48 general multiplications
  * per lane and coset instead of 63.  Taken where the evaluation generator is the domains' own root of unity of order L (every
  * ArithmeticDomain's is; any offset); other generators run the table form whatever the value.  The same words either way. */
 #define TVM_OPTION_LDE_PASS2_SCALE_ABSORBED 12
+/* TVM_OPTION_COMBINATION_FROM_COEFFICIENTS (default 1): tvm_evaluate_extended takes its route (below); 0: it answers TVM_NOT_APPLICABLE
+ * whatever the shape, so that a host that falls back to tvm_evaluate runs the general transform (A/B).  The same words either way. */
+#define TVM_OPTION_COMBINATION_FROM_COEFFICIENTS 13
 int32_t tvm_ctx_set_option(tvm_ctx* ctx, int32_t option, uint64_t value);
+/* The value an option has now, for the options whose start value depends on the device or that select between two routes to the
+ * same words (ids 10 to 13: a fresh context answers the device's compute-unit count, 1, 1, 1); TVM_ERR_INVALID_ARGUMENT for others. */
+int32_t tvm_ctx_get_option(const tvm_ctx* ctx, int32_t option, uint64_t* value);
 /* Cap on the bytes this context may hold through tvm_malloc / table handles (0 = no cap).  Requests beyond it fail
  * with TVM_ERR_OUT_OF_MEMORY exactly like a full device: the knob a host uses to share a GPU, and what the tests use to
  * walk the reference's out-of-memory fallback (master_table.rs:268-271 -> the coset-wise path). */
@@ -183,6 +189,15 @@ int32_t tvm_dft16_selfcheck(tvm_ctx* ctx, int32_t form, const uint64_t* d_in, ui
  * elements.  evaluate accepts n_coeffs > domain.length (chunk folding, :153-167). */
 int32_t tvm_evaluate(tvm_ctx* ctx, int32_t field_kind, const uint64_t* d_coeffs, uint64_t n_coeffs,
                      tvm_domain domain, uint64_t* d_values);
+/* The same values, word for word, for a polynomial a few times shorter than the domain -- the prover's combination of the trace
+ * columns, trace length + randomizers coefficients on the short domain.  With n the largest power of two in n_coeffs the polynomial
+ * is lo + X^n hi = (lo + hi) + (X^n - 1) hi, an n-coefficient interpolant plus zerofier times randomizer: one relayout pass over
+ * the coefficients, the forward half of tvm_lde_table's extension into a scratch table, one pass that writes d_values in domain
+ * order.  Taken where n >= 16, 2 <= domain.length / n <= 32 and domain.generator is the domains' own root of unity of its order
+ * (ArithmeticDomain's; any offset), under TVM_OPTION_COMBINATION_FROM_COEFFICIENTS.  Elsewhere the status is TVM_NOT_APPLICABLE and
+ * nothing is written: call tvm_evaluate. */
+int32_t tvm_evaluate_extended(tvm_ctx* ctx, int32_t field_kind, const uint64_t* d_coeffs, uint64_t n_coeffs,
+                              tvm_domain domain, uint64_t* d_values);
 int32_t tvm_interpolate(tvm_ctx* ctx, int32_t field_kind, const uint64_t* d_values, tvm_domain domain,
                         uint64_t* d_coeffs);
 /* twenty-first `ntt` / `intt` (used at stark.rs:872,877,997,1002,1176): in place, natural order,

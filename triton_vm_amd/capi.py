@@ -58,6 +58,7 @@ _SIGNATURES = {
     "tvm_free": (C.c_int32, [C.c_void_p, C.c_void_p]),
     "tvm_ctx_trim": (C.c_int32, [C.c_void_p]),
     "tvm_ctx_set_option": (C.c_int32, [C.c_void_p, C.c_int32, C.c_uint64]),
+    "tvm_ctx_get_option": (C.c_int32, [C.c_void_p, C.c_int32, C.POINTER(C.c_uint64)]),
     "tvm_ctx_set_memory_limit": (C.c_int32, [C.c_void_p, C.c_size_t]),
     "tvm_ctx_memory_held": (C.c_int32, [C.c_void_p, C.POINTER(C.c_size_t)]),
     "tvm_ctx_memory_info": (C.c_int32, [C.c_void_p, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
@@ -77,6 +78,7 @@ _SIGNATURES = {
     "tvm_field_op": (C.c_int32, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]),
     "tvm_dft16_selfcheck": (C.c_int32, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_uint64]),
     "tvm_evaluate": (C.c_int32, [C.c_void_p, C.c_int32, C.c_void_p, C.c_uint64, Domain, C.c_void_p]),
+    "tvm_evaluate_extended": (C.c_int32, [C.c_void_p, C.c_int32, C.c_void_p, C.c_uint64, Domain, C.c_void_p]),
     "tvm_interpolate": (C.c_int32, [C.c_void_p, C.c_int32, C.c_void_p, Domain, C.c_void_p]),
     "tvm_ntt": (C.c_int32, [C.c_void_p, C.c_int32, C.c_void_p, C.c_uint64, C.c_uint64]),
     "tvm_intt": (C.c_int32, [C.c_void_p, C.c_int32, C.c_void_p, C.c_uint64, C.c_uint64]),
@@ -325,6 +327,22 @@ class Context:
         """TVM_OPTION_LDE_PASS2_SCALE_ABSORBED: the middle pass of the table extension folds the coset scale into its butterflies and
         twiddle tables instead of multiplying by it in every coset (A/B).  The same words either way."""
         self._check(self.lib.tvm_ctx_set_option(self.handle, 12, 1 if on else 0), "tvm_ctx_set_option")
+
+    def combination_from_coefficients(self, on=True):
+        """TVM_OPTION_COMBINATION_FROM_COEFFICIENTS: tvm_evaluate_extended takes its route (the default); off: it answers
+        TVM_NOT_APPLICABLE and its callers run tvm_evaluate (A/B).  The same words either way."""
+        self._check(self.lib.tvm_ctx_set_option(self.handle, 13, 1 if on else 0), "tvm_ctx_set_option")
+
+    def lde_pass1_workgroups(self, n=0):
+        """TVM_OPTION_LDE_PASS1_WORKGROUPS: workgroups per launch of the first LDE pass's row kernels (0: one per item; a context
+        starts with its device's compute-unit count).  The same words for every value."""
+        self._check(self.lib.tvm_ctx_set_option(self.handle, 10, n), "tvm_ctx_set_option")
+
+    def option(self, option_id):
+        """tvm_ctx_get_option: the value option 10, 11, 12 or 13 has now"""
+        v = C.c_uint64(0)
+        self._check(self.lib.tvm_ctx_get_option(self.handle, option_id, C.byref(v)), "tvm_ctx_get_option")
+        return v.value
 
     def check_constraints(self, d_main_trace, d_aux_trace, n_rows, challenges, seed=None, capacity=1024):
         """tvm_check_constraints: the AIR on the trace itself (initial constraints on row 0, consistency on every row, transition on

@@ -242,6 +242,29 @@ int32_t tvm_evaluate(tvm_ctx* c, int32_t fk, const uint64_t* d_coeffs, uint64_t 
     return TVM_OK;
 }
 
+// The same codeword by the route of the quotient segments (quotient_segments_of_coefficients): the polynomial is known by its
+// coefficients and is a few times shorter than the domain, so it enters the table extension behind the inverse transforms.  The
+// values land in a scratch table of one column in the order of the last LDE pass; one more pass writes them in domain order.
+int32_t tvm_evaluate_extended(tvm_ctx* c, int32_t fk, const uint64_t* d_coeffs, uint64_t n_coeffs, tvm_domain dom, uint64_t* d_values) {
+    if (!c || !d_values || (n_coeffs && !d_coeffs) || !valid_fk(fk) || !valid_domain(dom))
+        return set_error(c, TVM_ERR_INVALID_ARGUMENT, "tvm_evaluate_extended arguments");
+    const u64 L = dom.length;
+    if (!c->combination_from_coefficients || n_coeffs < 16 || n_coeffs > L) return TVM_NOT_APPLICABLE;
+    u64 n = 16;
+    while (2 * n <= n_coeffs) n <<= 1;
+    const u64 h = n_coeffs - n;   // (< n)
+    if (2 * n > L || L / n > 32 /* ntt.hip: TVM_LDE_MAX_COSETS */ || !lde_standard_root(dom.generator, L)) return TVM_NOT_APPLICABLE;
+    const TabLayout layout = lde_table_layout(n, L);
+    u64* form = (u64*)scratch(c, Scratch::CombinationForm, (size_t)fk * (n + h) * sizeof(u64));
+    u64* table = (u64*)scratch(c, Scratch::CombinationTable, (size_t)tvm_tab_words(layout.storage_rows(), (u64)fk) * sizeof(u64));
+    if (!form || !table) return set_error(c, TVM_ERR_OUT_OF_MEMORY, "evaluate_extended scratch");
+    u64* rnd = h ? form + (size_t)fk * n : nullptr;
+    TVM_TRY(lde_coefficient_form(c, d_coeffs, n_coeffs, fk, 0, fk, fk, n, h, form, rnd));
+    const LdeSplit split{2, form, 0, (int)fk};
+    TVM_TRY(lde_table(c, fk, nullptr, n, 1, rnd, h, bfe_pow(dom.generator, L / n), dom.offset, dom.generator, L, table, 0, &split));
+    return table_rows(c, table, layout, fk, d_values);   // (the successor blocks stay unfilled: nothing reads them)
+}
+
 // ---------------------------------------------------------------------------------- master-table LDE
 int32_t tvm_lde_table(tvm_ctx* c, int32_t fk, const uint64_t* d_trace, uint64_t n_rows, uint64_t n_cols,
                       const uint64_t* d_rnd, uint64_t h, tvm_domain trace_dom, tvm_domain eval_dom, tvm_table** out) {

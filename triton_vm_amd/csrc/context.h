@@ -111,6 +111,10 @@ namespace tvm {
 //   * tvm_stir_next_polynomial holds StirValues, StirQuotientSet and StirAnswerValues across tvm_evaluate and tvm_interpolate;
 //   * tvm_check_constraints holds its first six across air_on_rows (AirAccumulators; the selectors take the place of the zerofier
 //     inverses), and takes the last two after the screen's results are on the host.
+//   * tvm_evaluate_extended holds CombinationForm and CombinationTable across lde_coefficient_form, lde_table (pool blocks and cached
+//     tables only) and table_rows; it calls no entry point, and no entry point calls it.  Slots of its own, not the segment step's
+//     SegmentValues: the segment table's intermediates and the combination's differ in size by a factor of five, and a shared slot
+//     would be freed and allocated again (a drained stream each time) twice per proof.
 // A new unit takes NEW enumerators in the layer it calls from; it shares an existing one only where this comment says why it may.
 enum class Scratch : int {
     // ---- unit slots
@@ -150,6 +154,8 @@ enum class Scratch : int {
     AirCheckPairs,          // ... and their words
     MiddleBlock,            // tvm_out_of_domain_to_deep: the block that goes back to the host and the weight vectors behind it, held
                             // across out_of_domain_rows, poly_eval, ntt_columns (unit slots) and tvm_evaluate (helper and unit slots)
+    CombinationForm,        // tvm_evaluate_extended: the polynomial in coefficient form, its upper part behind it as the randomizers
+    CombinationTable,       // ... and its values as a table of one column in the order of the last LDE pass
     Count
 };
 // The kinds of constant table a context caches (cached_table); what the three key words mean is the kind's own business:
@@ -180,9 +186,11 @@ struct tvm_ctx {
     bool air_valid_trace = false;                       // TVM_OPTION_AIR_VALID_TRACE (capi.hip: tvm_all_quotients_combined)
     int lde_chunk_columns = 0;                          // TVM_OPTION_LDE_CHUNK_COLUMNS: 0 = chosen by lde_table (ntt.hip)
     int lde_pass2_tiles = 0;                            // TVM_OPTION_LDE_PASS2_TILES: 1 = the tile kernels instead of k_lde_pass2_fused (A/B)
-    bool lde_pass2_scale_absorbed = false;              // TVM_OPTION_LDE_PASS2_SCALE_ABSORBED (ntt.hip: lde_table, k_lde_pass2_fused)
-    u64 lde_pass1_workgroups = 0;                      // TVM_OPTION_LDE_PASS1_WORKGROUPS: 0 = one per (column, tile) item (lde_plan.h)
+    bool lde_pass2_scale_absorbed = true;               // TVM_OPTION_LDE_PASS2_SCALE_ABSORBED (ntt.hip: lde_table, k_lde_pass2_fused)
+    u64 lde_pass1_workgroups = 0;                      // TVM_OPTION_LDE_PASS1_WORKGROUPS: 0 = one per (column, tile) item (lde_plan.h);
+                                                        // tvm_ctx_create starts it at the device's compute-unit count (0 where it reports none)
     bool segments_from_coefficients = true;             // TVM_OPTION_SEGMENTS_FROM_COEFFICIENTS (capi.hip: quotient_segments_of_coefficients)
+    bool combination_from_coefficients = true;          // TVM_OPTION_COMBINATION_FROM_COEFFICIENTS (capi.hip: tvm_evaluate_extended)
     u64 merkle_min_workgroups = 4096;                  // TVM_OPTION_MERKLE_MIN_WORKGROUPS (hash.hip: merkle_tree_from_leaves)
     bool merkle_subtrees = true;                        // TVM_OPTION_MERKLE_SUBTREES: narrow levels seven to a launch (k_merkle_subtrees)
     std::string last_error;

@@ -27,6 +27,22 @@ bool bind_device(tvm_ctx* c) {
     return hipSetDevice(c->device) == hipSuccess;
 }
 
+// The device's compute units (256 on an MI355X); 0 where it reports none -- the CPU emulation has no such thing, and a driver that
+// refuses the question leaves the caller at the value that asks for nothing.
+static u64 compute_units(int device) {
+#ifdef TVM_EMU
+    (void)device;
+    return 0;
+#else
+    int n = 0;
+    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess) {
+        (void)hipGetLastError();
+        return 0;
+    }
+    return n > 0 ? (u64)n : 0;
+#endif
+}
+
 // ---- the table cache
 u64* cached_table(tvm_ctx* c, TableKind kind, u64 a, u64 b, u64 d, u64 words, bool* is_new) {
     const auto key = std::make_tuple(kind, a, b, d);
@@ -244,6 +260,7 @@ int32_t tvm_ctx_create(int32_t device, void* hip_stream, tvm_ctx** out) {
     tvm_ctx* c = new (std::nothrow) tvm_ctx();
     if (!c) return TVM_ERR_OUT_OF_MEMORY;
     c->device = device;
+    c->lde_pass1_workgroups = compute_units(device);   // LDE pass 1 starts with a workgroup per compute unit (context.h)
     if (hip_stream) {
         c->stream = (hipStream_t)hip_stream;
     } else {
@@ -377,11 +394,25 @@ int32_t tvm_ctx_set_option(tvm_ctx* c, int32_t option, uint64_t value) {
         c->segments_from_coefficients = value != 0;
         return TVM_OK;
     }
+    if (option == TVM_OPTION_COMBINATION_FROM_COEFFICIENTS) {
+        c->combination_from_coefficients = value != 0;
+        return TVM_OK;
+    }
     if (option == TVM_OPTION_MERKLE_MIN_WORKGROUPS) {
         c->merkle_min_workgroups = value ? value : 4096;
         return TVM_OK;
     }
     return set_error(c, TVM_ERR_INVALID_ARGUMENT, "unknown option");
+}
+int32_t tvm_ctx_get_option(const tvm_ctx* c, int32_t option, uint64_t* value) {
+    if (!c || !value) return TVM_ERR_INVALID_ARGUMENT;
+    switch (option) {
+        case TVM_OPTION_LDE_PASS2_SCALE_ABSORBED: *value = c->lde_pass2_scale_absorbed; return TVM_OK;
+        case TVM_OPTION_LDE_PASS1_WORKGROUPS: *value = c->lde_pass1_workgroups; return TVM_OK;
+        case TVM_OPTION_SEGMENTS_FROM_COEFFICIENTS: *value = c->segments_from_coefficients; return TVM_OK;
+        case TVM_OPTION_COMBINATION_FROM_COEFFICIENTS: *value = c->combination_from_coefficients; return TVM_OK;
+        default: return TVM_ERR_INVALID_ARGUMENT;
+    }
 }
 int32_t tvm_ctx_trim(tvm_ctx* c) {
     if (!c) return TVM_ERR_INVALID_ARGUMENT;

@@ -15,6 +15,8 @@ int lde_table(tvm_ctx* c, int fk, const u64* trace, u64 n_rows, u64 n_cols, cons
 // lde_table reads with LdeSplit mode 2 ([ncols][n_rows] words) and the randomizers of that call ([ncols / fk][h][fk])
 int lde_coefficient_form(tvm_ctx* c, const u64* in, u64 in_len, int in_fk, u64 in_col_stride, int ncols, int fk, u64 n_rows, u64 h,
                          u64* coeffs, u64* rnd);
+// is w the domains' own root of unity of order n (ArithmeticDomain's generator: the one the row and fused kernels are built for)?
+bool lde_standard_root(u64 w, u64 n);
 // hash.hip
 int hash_rows(tvm_ctx* c, const u64* table, const TabLayout& layout, int W, u64 stride, u64* digests);
 int merkle_tree_from_leaves(tvm_ctx* c, u64* nodes, u64 n_leaves);
@@ -33,6 +35,8 @@ int randomizer_contribution(tvm_ctx* c, int fk, const u64* rnd, u64 n, u64 n_col
 int randomized_segments(tvm_ctx* c, const u64* d_q_coeffs, u64 q_len, const u64* d_rnd, u64 n_rand, u64 zeta, u64 poly_len,
                         u64* d_polys);
 int table_lincomb(tvm_ctx* c, const u64* table, const TabLayout& layout, int fk, u64 n_cols, u64 stride, const u64* d_w, u64* d_out);
+// the rows of a table of W <= 3 words in domain order, d_out[row][W] (the tiles of table_lincomb; short axes: table_to_row_major)
+int table_rows(tvm_ctx* c, const u64* table, const TabLayout& layout, int W, u64* d_out);
 int poly_eval(tvm_ctx* c, const u64* d_coeffs, u64 n, const u64* d_points, int n_points, u64* d_out);
 int deep_sum(tvm_ctx* c, int n_comp, const u64* const* d_cw, const u64* h_points, const u64* h_values, const u64* h_weights,
              u64 offset, u64 gen, u64 n, u64* d_out);

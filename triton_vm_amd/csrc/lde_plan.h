@@ -102,9 +102,9 @@ inline LdePass lde_generic_pass(LdeKernel kernel, int log_axis, int batch_log, i
 }
 
 // Workgroups of a launch of pass 1's persistent row kernels over `items` work items: option (TVM_OPTION_LDE_PASS1_WORKGROUPS) of them,
-// never more than there are items.  0, the default, and any count at or above the items: ONE tile per workgroup, no second trip
-// through the loop.  (Measured at 2^20 rows with a workgroup per compute unit, 256 for 6144 items: the kernel -13 %, a proof -0.4 % --
-// inside the spread of a proof's time from run to run, so the walking grid is not the default: DESIGN.md 9.)
+// never more than there are items.  0 and any count at or above the items: ONE tile per workgroup, no second trip through the loop.
+// (Measured at 2^20 rows with a workgroup per compute unit, 256 for 6144 items: the kernel -13 %.  A context starts with its device's
+// compute-unit count -- context.hip, the one unit that asks the device; this header only does the arithmetic: DESIGN.md 9.)
 inline std::uint64_t lde_pass1_workgroups(std::uint64_t items, std::uint64_t option) {
     const std::uint64_t g = option ? option : items;
     return g < items ? g : (items ? items : 1);

@@ -860,10 +860,11 @@ __global__ void k_pass3_halves_table(const u64* __restrict__ tw_2048, u64* __res
 // its NEXT item as soon as the current tile is complete in LDS -- they are in flight under the butterflies and the store phase, and
 // go into LDS after it.  No barrier between the store phase and that fill: a work-item reads, in the store phase, exactly the 16
 // words (row b, positions q0 + LPR it) that it fills, so it overwrites nothing another work-item still has to read; the two
-// barriers of a tile are "tile complete" and "rows transformed".  With a workgroup per item -- the default,
-// TVM_OPTION_LDE_PASS1_WORKGROUPS = 0 -- the phases of a tile run one after the other (one workgroup per CU at 1024 points: while a
-// tile loads nothing is issued, while it is transformed nothing is in flight); with a workgroup per compute unit the kernel is
-// 13 % faster at 2^20 rows (profiles/lde_pass1_*), which a proof's time does not resolve: not the default.
+// barriers of a tile are "tile complete" and "rows transformed".  With a workgroup per item -- TVM_OPTION_LDE_PASS1_WORKGROUPS = 0 --
+// the phases of a tile run one after the other (one workgroup per CU at 1024 points: while a tile loads nothing is issued, while it
+// is transformed nothing is in flight); with a workgroup per compute unit the kernel is 13 % faster at 2^20 rows
+// (profiles/lde_pass1_*).  A context starts with the compute-unit count of its device (context.hip: tvm_ctx_create),
+// the CPU emulation, which has none, with 0.
 template <int LOGN, int ROWS>
 __global__ void __launch_bounds__((1 << (LOGN - 4)) * ROWS, 4) k_lde_pass1_rows(Ntt2Args a) {
     // LOGN = 10: one wavefront per row, 16 rows (128-byte runs of the input).  LOGN = 11 (round 5; 2^22 and 2^23-row traces): TWO
@@ -1437,6 +1438,8 @@ static int classify_root(u64 w, u64 n) {
     if (r == bfe_pow(two, (u64)((36 << (4 - k)) % 192))) return 2;
     return 0;
 }
+
+bool lde_standard_root(u64 w, u64 n) { return is_pow2(n) && n >= 2 && classify_root(w, n) == 1; }
 
 // What every two-pass transform fills the same way: the shape, the column step's twiddles for root w, the inter-pass twiddles;
 // no scaling, the identity output map, virtual column 0.  (in, out, tmp, in_len, the strides and field kinds, tw2 and root are

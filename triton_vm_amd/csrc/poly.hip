@@ -12,7 +12,7 @@
 // All of these are streaming kernels: one pass over their operands, HBM bound.
 
 #include "air_eval.h"   // AirAcc: sums of products with one reduction per coefficient at the end
-#include "context.h"
+#include "kernels.h"   // (and context.h): table_rows hands short axes to hash.hip's table_to_row_major
 
 namespace tvm {
 
@@ -445,6 +445,37 @@ __global__ void __launch_bounds__(256) k_table_lincomb_tiles(const u64* __restri
     }
 }
 
+// The rows themselves in place of a combination of their words: a table of W <= 3 words per row (one column of either field: the
+// combination codeword, capi.hip: tvm_evaluate_extended) -> out[domain row][W].  The same tiles -- 16 rows j2 x 128 (j1, coset)
+// pairs, full lines in, through shared memory, runs of 128 (at most eight cosets) or eight consecutive domain rows out.
+__global__ void __launch_bounds__(256) k_table_rows_tiles(const u64* __restrict__ table, TabView view, int W, u64* __restrict__ out) {
+    constexpr int RS = 3 * TVM_LINCOMB_TILE_PAIRS + 1;
+    __shared__ u64 so[16 * RS];
+    const TabLayout& l = view.l;
+    const int tid = threadIdx.x, p = tid & 15, q = tid >> 4;
+    const int log_kx = view.log_xv < 3 ? view.log_xv : 3, kx = 1 << log_kx;
+    const int j1_per_tile = TVM_LINCOMB_TILE_PAIRS >> log_kx;
+    u64 b = blockIdx.x;   // tile coordinates as in k_table_lincomb_tiles
+    const u64 P = (b & ((l.n1 >> 4) - 1)) << 4;
+    b >>= l.log_n1 - 4;
+    const u64 tiles_j1 = l.n2 / j1_per_tile;
+    const u64 J = (b % tiles_j1) * j1_per_tile, k0 = (b / tiles_j1) << log_kx;
+    for (int it = 0; it < TVM_LINCOMB_TILE_PAIRS / 16; it++) {
+        const int pair = q + 16 * it;
+        const u64 j1 = J + (pair >> log_kx), kv = k0 + (pair & (kx - 1));
+        const u64 row = kv * view.stride * l.pitch + j1 * l.n1 + P + p;
+        for (int v = 0; v < W; v++) so[p * RS + W * pair + v] = TVM_LOAD_STREAM(&table[tvm_tab_idx(row, (u64)v, (u64)W)]);
+    }
+    __syncthreads();
+    const int run = W * TVM_LINCOMB_TILE_PAIRS;
+    for (int e = tid; e < 16 * run; e += 256) {
+        const int pp = e / run, word = e % run, pair = word / W, comp = word % W;
+        const u64 j = J + (pair >> log_kx) + ((P + pp) << l.log_n2);   // coset_index of the row
+        const u64 i = (j << view.log_xv) + k0 + (pair & (kx - 1));
+        out[(u64)W * i + comp] = so[pp * RS + word];
+    }
+}
+
 // polynomial (XFE coefficients) at XFE points: partial[p][block] then a final pass
 __global__ void __launch_bounds__(TVM_RED_BLOCK) k_poly_eval_partial(const u64* __restrict__ co, u64 n,
                                                                      const u64* __restrict__ points,
@@ -648,6 +679,15 @@ int table_lincomb(tvm_ctx* c, const u64* table, const TabLayout& layout, int fk,
             TVM_LAUNCH(k_table_lincomb_tiles<0>, dim3((unsigned)tiles), dim3(256), 0, c->stream, table, view, fk, n_cols, d_w, d_out);
     } else
         TVM_LAUNCH(k_table_lincomb, TVM_GRID(view.n_out, 256), dim3(256), 0, c->stream, table, view, fk, n_cols, d_w, d_out);
+    TVM_HIP_CHECK(c, hipGetLastError());
+    return TVM_OK;
+}
+int table_rows(tvm_ctx* c, const u64* table, const TabLayout& layout, int W, u64* d_out) {
+    const TabView view = tab_view(layout, 1);
+    const u64 j1_per_tile = TVM_LINCOMB_TILE_PAIRS / (layout.X < 8 ? layout.X : 8);
+    if (W > 3 || !view.by_coset || layout.n1 < 16 || layout.n2 < j1_per_tile)   // short axes (traces below 2^12 rows or so): a word per work-item
+        return table_to_row_major(c, table, layout, W, d_out);
+    TVM_LAUNCH(k_table_rows_tiles, dim3((unsigned)(view.n_out / (16 * TVM_LINCOMB_TILE_PAIRS))), dim3(256), 0, c->stream, table, view, W, d_out);
     TVM_HIP_CHECK(c, hipGetLastError());
     return TVM_OK;
 }

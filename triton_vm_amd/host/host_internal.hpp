@@ -119,6 +119,11 @@ protected:
     // 15: the weighted sums wp, wr of the segments on this rank's rows of the short domain: rows of the segment table
     virtual void segment_combinations(const tvm_table* segments, const DeviceBuffer& polys, u64 poly_len, const ArithmeticDomain& short_rank,
                                       const Xfe* wp, const Xfe* wr, DeviceBuffer& cw_p, DeviceBuffer& cw_r);
+    // 15: the combination of the trace columns (n_comb coefficients, XFE) on this rank's rows of the short domain.  A rank's share of
+    // a domain is the general transform's business; the prover that holds the whole domain has a shorter route (WholeSteps)
+    virtual DeviceBuffer combination_codeword(const ArithmeticDomain& short_rank, const DeviceBuffer& comb, u64 n_comb) {
+        return short_rank.evaluate(c, comb.ptr(), n_comb, 3);
+    }
     // FRI: the rounds whose tree is split over the ranks (roots enqueued, challenges sampled, folds done), appended to `rounds`;
     // `dom` moves on to the first round that is not.  -> that round's codeword in row order (after the last round: the last codeword)
     virtual DeviceBuffer fri_distributed_rounds(DeviceBuffer&& codeword, std::vector<FriRound>& /*rounds*/, ArithmeticDomain& /*dom*/) {

@@ -674,7 +674,7 @@ DeviceBuffer ProofSteps::host_middle(const tvm_table* segments, const DeviceBuff
         c.check(tvm_xfe_add_assign(c.raw(), comb.ptr(), comb_aux.ptr(), 2 * p.trace.length), "tvm_xfe_add_assign");
     }
     const u64 n_comb = p.trace.length + p.h;
-    const DeviceBuffer main_aux_codeword = short_rank.evaluate(c, comb.ptr(), n_comb, 3);
+    const DeviceBuffer main_aux_codeword = combination_codeword(short_rank, comb, n_comb);
     std::vector<Xfe> wp = weights_q, wr = weights_q;
     wp[4] = Xfe{{0, 0, 0}};
     wr[0] = Xfe{{0, 0, 0}};
@@ -894,6 +894,16 @@ struct WholeSteps : ProofSteps {
             c.check(tvm_quotient_segments(c.raw(), quot.ptr(), p.quotient.c(), p.ldt.c(), quotient_randomizer.data()->c,
                                           quotient_randomizer.size(), zeta, &seg, polys.ptr(), poly_len), "tvm_quotient_segments");
         return seg;
+    }
+    // The combination has trace length + randomizers coefficients and the short domain a few times as many points: the forward half
+    // of the table extension from the coefficients (tvm_evaluate_extended), and only where that does not apply (traces below 16 rows,
+    // other expansion factors, TVM_OPTION_COMBINATION_FROM_COEFFICIENTS = 0) the general transform.  The same words either way.
+    DeviceBuffer combination_codeword(const ArithmeticDomain& short_rank, const DeviceBuffer& comb, u64 n_comb) override {
+        DeviceBuffer out(c, short_rank.length * 3);
+        const int32_t status = tvm_evaluate_extended(c.raw(), 3, comb.ptr(), n_comb, short_rank.c(), out.ptr());
+        if (status == TVM_NOT_APPLICABLE) return ProofSteps::combination_codeword(short_rank, comb, n_comb);
+        c.check(status, "tvm_evaluate_extended");
+        return out;
     }
     // the three trees have the same shape and the same revealed leaves, hence the same authentication-structure node indices;
     // their nodes come back in one round trip
