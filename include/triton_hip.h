@@ -384,7 +384,8 @@ int32_t tvm_all_quotients_combined(tvm_ctx* ctx, const tvm_table* main_table, co
  * d_coeffs: capacity XFE, at least 4 * trace_domain.length + n1 (n1 = the rows of one block of the tables; quotient_domain.length always
  * suffices); *n_coeffs: the number written -- every coefficient of the quotient beyond it is zero.  Evaluated on the quotient domain they
  * are the codeword of tvm_all_quotients_combined, word for word (valid trace).  TVM_NOT_APPLICABLE, *n_coeffs = 0 and nothing written
- * where those conditions do not hold: call tvm_all_quotients_combined. */
+ * where those conditions do not hold: call tvm_all_quotients_combined.  (The conditions, as code: the remainder route of
+ * csrc/quotient_plan.h, which decides the route of both entry points.) */
 int32_t tvm_all_quotients_coefficients(tvm_ctx* ctx, const tvm_table* main_table, const tvm_table* aux_table,
                                        tvm_domain trace_domain, tvm_domain quotient_domain,
                                        const uint64_t* h_challenges, const uint64_t* h_weights,
@@ -409,7 +410,7 @@ int32_t tvm_check_constraints(tvm_ctx* ctx, const uint64_t* d_main_trace, const 
  * constraints are generated in four classes by the length of their quotients: bit 0 = the initial / terminal quotients of degree-4
  * constraints (needed on every point of the quotient domain), bit 1 = "half" (fewer than 4N coefficients), bit 2 = "quarter"
  * (fewer than 2N), bit 3 = "three cosets" (fewer than 3N).  tvm_air_class_cosets: how many cosets of the trace domain determine
- * each class's quotient polynomial for these tables' interpolant lengths (out[class bit]; 0 = the degree bound does not hold: use
+ * each class's quotient polynomial for these tables' interpolant lengths (out[class bit]; 0 = the degree bound -- csrc/quotient_plan.h: fits -- does not hold: use
  * tvm_all_quotients_combined on every point).  tvm_air_class_values: sum over the constraints of the classes in class_mask of
  * weight * constraint * zerofier inverse on coset `coset` of table_domain (the domain the tables were extended onto; X = its
  * length / N cosets, coset k = the points k + X j) -> trace_domain.length XFE in the coset's natural order.

@@ -1,5 +1,5 @@
 // capi.hip -- the extern "C" boundary of libtriton_hip.so (declared in include/triton_hip.h), the context's own entry points
-// apart (context.hip).  Argument validation and error mapping live here, and the small kernels that belong to no unit of their own
+// and the AIR quotient's apart (context.hip, quotient.hip).  Argument validation and error mapping live here, and the small kernels that belong to no unit of their own
 // (synthetic data, the field self-check, folds, combinations, gathers); the large ones live in ntt.hip / hash.hip / poly.hip / air.hip.
 #include <cstring>
 #include <new>
@@ -12,7 +12,6 @@
 using namespace tvm;
 
 static bool valid_fk(int32_t fk) { return fk == 1 || fk == 3; }
-static bool valid_domain(const tvm_domain& d) { return is_pow2(d.length) && d.length >= 1 && d.generator < TVM_P && d.offset < TVM_P; }
 
 namespace tvm {
 // splitmix64 of (seed, index), reduced into [0, p): synthetic benchmark data only
@@ -464,111 +463,6 @@ extern "C" int32_t tvm_codeword_merkle_tree(tvm_ctx* c, const uint64_t* d_cw, ui
 
 // ---------------------------------------------------------------------------------- combination / DEEP / FRI
 namespace tvm {
-// coeffs[i + N * r] += sum_k w[3 * r + k] * q[k][i]  (r, k < 3; i < N; XFE vectors q, base-field weights w): the polynomial
-// A + X^N B + X^2N C from its restrictions Q_k = A + c_k B + c_k^2 C to three cosets (w = the inverse Vandermonde matrix)
-struct ThreeCosetWeights {
-    u64 w[9];
-};
-// coeffs[i * N + t] (+)= sum_j w[4 i + j] * q_j[t]  (i, j < n <= 4; t < N; XFE vectors q_j, base-field weights): the polynomial
-// sum_i X^(iN) A_i from its restrictions Q_j = sum_i c_j^i A_i to n cosets (w = the inverse Vandermonde matrix); added to coeffs, or
-// (accumulate = 0) stored -- the first summand of an array that is then never cleared
-struct CosetCombineWeights {
-    u64 w[16];
-};
-struct CosetCombinePointers {
-    const u64* q[4];
-};
-__global__ void k_coset_combine(CosetCombinePointers p, int n, u64 N, CosetCombineWeights m, u64* __restrict__ coeffs, int accumulate) {
-    const u64 t = (u64)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= N) return;
-    xfe v[4];
-    for (int j = 0; j < n; j++) v[j] = xfe_make(p.q[j][3 * t], p.q[j][3 * t + 1], p.q[j][3 * t + 2]);
-    for (int i = 0; i < n; i++) {
-        u64* o = coeffs + 3 * ((u64)i * N + t);
-        xfe acc = accumulate ? xfe_make(o[0], o[1], o[2]) : xfe_zero();
-        for (int j = 0; j < n; j++) acc = xfe_add(acc, xfe_mul_bfe(v[j], m.w[4 * i + j]));
-        o[0] = acc.c0, o[1] = acc.c1, o[2] = acc.c2;
-    }
-}
-// The inverse of the n x n Vandermonde matrix of cs[0 .. n-1] (n <= 4) into w (w[4 i + j], zero elsewhere): row i holds the coefficients
-// of x^i in the Lagrange basis polynomials L_j(x) = prod_{l != j} (x - c_l) / (c_j - c_l).  false if two of the c_j are equal.
-static bool coset_combine_weights(const u64* cs, uint32_t n, CosetCombineWeights& w) {
-    for (int i = 0; i < 16; i++) w.w[i] = 0;
-    for (uint32_t j = 0; j < n; j++) {
-        u64 poly[4] = {TVM_ONE, 0, 0, 0};   // running product prod (x - c_l), low coefficient first
-        u64 denom = TVM_ONE;
-        int deg = 0;
-        for (uint32_t l = 0; l < n; l++) {
-            if (l == j) continue;
-            if (cs[l] == cs[j]) return false;
-            for (int e = deg + 1; e >= 1; e--) poly[e] = bfe_sub(poly[e - 1], bfe_mul(poly[e], cs[l]));
-            poly[0] = bfe_neg(bfe_mul(poly[0], cs[l]));
-            deg++;
-            denom = bfe_mul(denom, bfe_sub(cs[j], cs[l]));
-        }
-        const u64 dinv = bfe_inv(denom);
-        for (uint32_t i = 0; i < n; i++) w.w[4 * i + j] = bfe_mul(poly[i], dinv);
-    }
-    return true;
-}
-// The remainder set (tvm_all_quotients_combined, valid-trace mode): partial[g][i] = sum_{r < R} d^(gR + r) sum_j lambda_j q_j[i + (gR + r) M]
-// for g < G, i < M -- the polynomial sum_j lambda_j q_j of G R M coefficients modulo X^M - d, as G partial sums (k_remainder_scatter
-// adds them up)
-struct RemainderFold {
-    const u64* q[4];
-    u64 lambda[4];
-    int n;
-};
-__global__ void k_remainder_fold(RemainderFold f, u64 M, u64 G, u64 R, u64 d, u64* __restrict__ partial) {
-    const u64 e = (u64)blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= G * M) return;
-    const u64 i = e % M, g = e / M;
-    u64 s = bfe_pow(d, g * R);
-    xfe acc = xfe_zero();
-    for (u64 r = 0; r < R; r++) {
-        const u64 row = 3 * (i + (g * R + r) * M);
-        xfe v = xfe_zero();
-        for (int j = 0; j < f.n; j++) v = xfe_add(v, xfe_mul_bfe(xfe_make(f.q[j][row], f.q[j][row + 1], f.q[j][row + 2]), f.lambda[j]));
-        acc = xfe_add(acc, xfe_mul_bfe(v, s));
-        s = bfe_mul(s, d);
-    }
-    partial[3 * e] = acc.c0, partial[3 * e + 1] = acc.c1, partial[3 * e + 2] = acc.c2;
-}
-// b = p[i] - sum_g partial[g][i] (the interpolant of q - R on the remainder set, i < M);  coeffs[i + k N] += v[k] * b, k < n_v
-struct RemainderScatter {
-    u64 v[5];
-    int n_v;
-};
-__global__ void k_remainder_scatter(const u64* __restrict__ p, const u64* __restrict__ partial, u64 G, u64 M, u64 N, RemainderScatter w,
-                                    u64* __restrict__ coeffs) {
-    const u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= M) return;
-    xfe b = xfe_make(p[3 * i], p[3 * i + 1], p[3 * i + 2]);
-    for (u64 g = 0; g < G; g++) {
-        const u64* x = partial + 3 * (g * M + i);
-        b = xfe_sub(b, xfe_make(x[0], x[1], x[2]));
-    }
-    for (int k = 0; k < w.n_v; k++) {
-        u64* o = coeffs + 3 * (i + (u64)k * N);
-        const xfe r = xfe_add(xfe_make(o[0], o[1], o[2]), xfe_mul_bfe(b, w.v[k]));
-        o[0] = r.c0, o[1] = r.c1, o[2] = r.c2;
-    }
-}
-__global__ void k_three_coset_combine(const u64* __restrict__ q0, const u64* __restrict__ q1, const u64* __restrict__ q2, u64 n,
-                                      ThreeCosetWeights m, u64* __restrict__ coeffs) {
-    const u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const xfe a = xfe_make(q0[3 * i], q0[3 * i + 1], q0[3 * i + 2]), b = xfe_make(q1[3 * i], q1[3 * i + 1], q1[3 * i + 2]),
-              c = xfe_make(q2[3 * i], q2[3 * i + 1], q2[3 * i + 2]);
-#pragma unroll
-    for (int r = 0; r < 3; r++) {
-        const xfe v = xfe_add(xfe_add(xfe_mul_bfe(a, m.w[3 * r]), xfe_mul_bfe(b, m.w[3 * r + 1])), xfe_mul_bfe(c, m.w[3 * r + 2]));
-        u64* p = coeffs + 3 * (i + n * r);
-        p[0] = bfe_add(p[0], v.c0);
-        p[1] = bfe_add(p[1], v.c1);
-        p[2] = bfe_add(p[2], v.c2);
-    }
-}
 // out[i] = sum_k w[k] * v[k * stride + i]  (XFE vectors, XFE weights; k < 8)
 __global__ void k_xfe_linear_combination(const u64* __restrict__ v, int n_vectors, u64 stride, u64 n, const u64* __restrict__ w,
                                          u64* __restrict__ out) {
@@ -894,363 +788,8 @@ int32_t tvm_extend_aux_table(tvm_ctx* c, const uint64_t* d_main_trace, uint64_t*
     return extend_aux_table(c, d_main_trace, d_aux_trace, staged, n_rows);
 }
 
-// Valid-trace mode, one coset fewer per class (tvm_all_quotients_combined below).  A class's quotient q has fewer than nN + s coefficients,
-// s <= M = n1 (the rows of one block of the tables).  With S the n cosets gamma_k <w_N> (X^N = c_k there) and V(X) = prod_{k in S} (X^N - c_k),
-//   q = R + V B,  deg R < nN,  deg B < s:
-// R is the interpolant of q's values on S -- n N-point interpolations Q_k, combined by the inverse Vandermonde matrix of the c_k
-// (k_coset_combine, as tvm_coset_values_to_coefficients).  B comes from q on ONE BLOCK T of another coset: its n1 storage rows are the
-// points tau w_M^i, i < M (tau = gamma_T w_N^0, w_M = w_N^n2, a coset of the order-M subgroup) and their successors are the next block
-// (context.h), so the AIR evaluates them like a coset of their own (air_quotients_on_block).  On T, X^N is the constant c'' = gamma_T^N
-// and V the constant beta = prod (c'' - c_k); R restricted to gamma_T <w_N> is sum_k L_k(c'') Q_k (L_k the Lagrange basis in the c_k),
-// which modulo X^M - tau^M is the interpolant of R on T (k_remainder_fold).  So B = (interpolant of q on T - that fold) / beta, and V B
-// adds v_i / beta times it at the coefficients i N + (0 .. M-1) (k_remainder_scatter).  On a valid trace B's coefficients s .. M-1 are zero.
-// Class 0 (the initial / terminal quotients of the four degree-4 constraints: fewer than 4 (m - 1) + 1 <= 4N + M coefficients) goes the
-// same way when the caller wants COEFFICIENTS (tvm_all_quotients_coefficients): S = the cosets 0, 2, 4, 6 and T block 0 of coset 1 (the
-// even cosets are used up; the tables hold all eight) -- half the rows of the row-by-row evaluation on the quotient domain, and no
-// codeword of 8N points on the way.  The coefficient array is then 4N + M long.
-namespace tvm {
-// coeffs: [4N] XFE (classes 1, 3, 2), or [4N + M] with class 0; every element is written
-static int remainder_coset_coefficients(tvm_ctx* c, const tvm_table* mt, const tvm_table* at, tvm_domain td, tvm_domain qd, const u64* d_ch,
-                                        const u64* d_w, bool with_class_0, u64* coeffs) {
-    const u64 N = td.length, M = mt->layout.n1, n2 = mt->layout.n2, pitch = mt->layout.pitch, X = qd.length / N;
-    const u64 G = n2 < 64 ? n2 : 64, R = n2 / G;   // the fold: G partial sums of R chunks of M coefficients
-    const u64 n_q = with_class_0 ? 4 : 3, n_coeffs = with_class_0 ? 4 * N + M : 4 * N;
-    PoolBlock block(c, (size_t)3 * (N + n_q * N + 2 * M + G * M) * sizeof(u64));   // released on every exit path
-    u64* vals = (u64*)block.p;     // [N] XFE: a class on one coset
-    if (!vals) return set_error(c, TVM_ERR_OUT_OF_MEMORY, "quotient scratch");
-    u64* q = vals + 3 * N;         // [n_q][N] XFE: its interpolants Q_k
-    u64* q_t = q + 3 * n_q * N;    // [M] XFE: a class on T, then ...
-    u64* p_t = q_t + 3 * M;        // ... its interpolant there
-    u64* partial = p_t + 3 * M;    // [G][M] XFE
-    const u64 g_n = bfe_pow(qd.generator, X), g_m = bfe_pow(g_n, n2);
-    // (the cosets of the tables ARE those of the quotient domain here: the gate asks for X == layout.X)
-    TabLayout lm = mt->layout;   // one coset of the tables: a table of its own
-    lm.X = 1;
-    lm.log_x = 0;
-    const int CLASS_FULL = 1 << 0, CLASS_HALF = 1 << 1, CLASS_QUARTER = 1 << 2, CLASS_THREE = 1 << 3;
-    struct {
-        int mask;
-        uint32_t n;   // S = the first n of the cosets 0, 2, 4, 6
-        u64 k_t;      // T = block 0 of this coset
-    } const classes[4] = {{CLASS_FULL, 4, 1}, {CLASS_HALF, 3, 6}, {CLASS_THREE, 2, 6}, {CLASS_QUARTER, 1, 6}};
-    bool first = true;
-    for (const auto& cl : classes) {
-        if (cl.mask == CLASS_FULL && !with_class_0) continue;
-        const u64 gamma_t = bfe_mul(qd.offset, bfe_pow(qd.generator, cl.k_t)), c_t = bfe_pow(gamma_t, N), d_t = bfe_pow(gamma_t, M);
-        const u64* main_t = mt->data + tvm_tab_idx(cl.k_t * pitch, 0, (u64)mt->W);
-        const u64* aux_t = at->data + tvm_tab_idx(cl.k_t * pitch, 0, (u64)at->W);
-        u64 cs[4];
-        CosetCombinePointers ptrs;
-        for (uint32_t j = 0; j < 4; j++) ptrs.q[j] = nullptr;
-        for (uint32_t j = 0; j < cl.n; j++) {
-            const u64 k = 2 * (u64)j;
-            const tvm_domain dom = {bfe_mul(qd.offset, bfe_pow(qd.generator, k)), g_n, N};
-            cs[j] = bfe_pow(dom.offset, N);
-            TVM_TRY(all_quotients_combined(c, mt->data + tvm_tab_idx(k * pitch, 0, (u64)mt->W), lm, (u64)mt->W,
-                                           at->data + tvm_tab_idx(k * pitch, 0, (u64)at->W), (u64)at->W, N, td.generator, dom.offset,
-                                           dom.generator, N, d_ch, d_w, vals, cl.mask, 0));
-            TVM_TRY(tvm_interpolate(c, 3, vals, dom, q + 3 * N * j));
-            ptrs.q[j] = q + 3 * N * j;
-        }
-        CosetCombineWeights w;
-        if (!coset_combine_weights(cs, cl.n, w)) return set_error(c, TVM_ERR_INVALID_ARGUMENT, "quotients: two cosets with the same X^N");
-        // (+)= R: the first class stores its n blocks and the rest of the array is cleared -- no pass over all of it beforehand
-        TVM_LAUNCH(k_coset_combine, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, c->stream, ptrs, (int)cl.n, N, w, coeffs, first ? 0 : 1);
-        if (first) TVM_HIP_CHECK(c, hipMemsetAsync(coeffs + 3 * cl.n * N, 0, (size_t)3 * (n_coeffs - cl.n * N) * sizeof(u64), c->stream));
-        first = false;
-        // R on T, modulo X^M - tau^M: the Lagrange weights L_j(c'') = sum_i c''^i w[4 i + j]
-        RemainderFold f;
-        f.n = (int)cl.n;
-        for (uint32_t j = 0; j < 4; j++) {
-            f.q[j] = ptrs.q[j];
-            f.lambda[j] = 0;
-        }
-        for (uint32_t j = 0; j < cl.n; j++) {
-            u64 ci = TVM_ONE;
-            for (uint32_t i = 0; i < cl.n; i++, ci = bfe_mul(ci, c_t)) f.lambda[j] = bfe_add(f.lambda[j], bfe_mul(ci, w.w[4 * i + j]));
-        }
-        TVM_LAUNCH(k_remainder_fold, dim3((unsigned)((G * M + 255) / 256)), dim3(256), 0, c->stream, f, M, G, R, d_t, partial);
-        // q on T, its interpolant there
-        TVM_TRY(air_quotients_on_block(c, main_t, (u64)mt->W, aux_t, (u64)at->W, M, N, td.generator, gamma_t, g_m, d_ch, d_w, q_t, cl.mask));
-        TVM_TRY(tvm_interpolate(c, 3, q_t, tvm_domain{gamma_t, g_m, M}, p_t));
-        // V = prod (Y - c_k) in Y = X^N, its coefficients divided by beta = V(c'')
-        RemainderScatter v;
-        v.n_v = (int)cl.n + 1;
-        u64 beta = TVM_ONE;
-        for (int i = 0; i < 5; i++) v.v[i] = 0;
-        v.v[0] = TVM_ONE;
-        for (uint32_t j = 0; j < cl.n; j++) {
-            for (int e = (int)j + 1; e >= 1; e--) v.v[e] = bfe_sub(v.v[e - 1], bfe_mul(v.v[e], cs[j]));
-            v.v[0] = bfe_neg(bfe_mul(v.v[0], cs[j]));
-            beta = bfe_mul(beta, bfe_sub(c_t, cs[j]));
-        }
-        const u64 beta_inv = bfe_inv(beta);
-        for (int i = 0; i < v.n_v; i++) v.v[i] = bfe_mul(v.v[i], beta_inv);
-        TVM_LAUNCH(k_remainder_scatter, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, c->stream, p_t, partial, G, M, N, v, coeffs);
-        TVM_HIP_CHECK(c, hipGetLastError());
-    }
-    return TVM_OK;
-}
-
-// the codeword: the coefficients of classes 1, 3, 2 evaluated on the quotient domain, class 0 added row by row
-static int quotients_by_remainder_coset(tvm_ctx* c, const tvm_table* mt, const tvm_table* at, tvm_domain td, tvm_domain qd, const u64* d_ch,
-                                        const u64* d_w, u64* d_out) {
-    const u64 N = td.length;
-    PoolBlock block(c, (size_t)12 * N * sizeof(u64));   // released on every exit path
-    u64* coeffs = (u64*)block.p;   // [4N] XFE: the sum of the classes' quotients
-    if (!coeffs) return set_error(c, TVM_ERR_OUT_OF_MEMORY, "quotient scratch");
-    TVM_TRY(remainder_coset_coefficients(c, mt, at, td, qd, d_ch, d_w, false, coeffs));
-    TVM_TRY(tvm_evaluate(c, 3, coeffs, 4 * N, qd, d_out));
-    return all_quotients_combined(c, mt->data, mt->layout, (u64)mt->W, at->data, (u64)at->W, N, td.generator, qd.offset, qd.generator,
-                                  qd.length, d_ch, d_w, d_out, 1 << 0, 1);
-}
-}  // namespace tvm
-
-// what tvm_all_quotients_combined and tvm_all_quotients_coefficients share: the checks of their arguments, the staging of the
-// challenges and weights, and (below) the gates of valid-trace mode
-static int quotient_arguments(tvm_ctx* c, const tvm_table* mt, const tvm_table* at, tvm_domain td, tvm_domain qd, const uint64_t* h_challenges,
-                              const uint64_t* h_weights, const uint64_t* d_out) {
-    if (!c || !mt || !at || !h_challenges || !h_weights || !d_out || !valid_domain(td) || !valid_domain(qd))
-        return set_error(c, TVM_ERR_INVALID_ARGUMENT, "all_quotients_combined arguments");
-    if (mt->fk != 1 || mt->n_cols != TVM_NUM_MAIN_COLUMNS || at->fk != 3 || at->n_cols != TVM_NUM_AUX_COLUMNS ||
-        mt->rows != at->rows || qd.length > mt->rows || !mt->has_successor_blocks || !at->has_successor_blocks ||
-        mt->layout.X != at->layout.X || mt->layout.n1 != at->layout.n1 || mt->layout.n2 != at->layout.n2 || mt->layout.pitch != at->layout.pitch)
-        return set_error(c, TVM_ERR_INVALID_ARGUMENT, "all_quotients_combined: tables must be 379 BFE / 91 XFE columns wide, made by tvm_lde_table over one domain");
-    return TVM_OK;
-}
-static int stage_quotient_inputs(tvm_ctx* c, const uint64_t* h_challenges, const uint64_t* h_weights, const u64** d_ch, const u64** d_w) {
-    u64* staged = (u64*)scratch(c, Scratch::QuotientInputs, (size_t)3 * (TVM_NUM_CHALLENGES + TVM_NUM_QUOTIENT_WEIGHTS) * sizeof(u64));
-    if (!staged) return set_error(c, TVM_ERR_OUT_OF_MEMORY, "challenge staging");
-    TVM_TRY(tvm::h2d_small(c, staged, h_challenges, 3 * TVM_NUM_CHALLENGES * sizeof(u64)));
-    TVM_TRY(tvm::h2d_small(c, staged + 3 * TVM_NUM_CHALLENGES, h_weights, 3 * TVM_NUM_QUOTIENT_WEIGHTS * sizeof(u64)));
-    *d_ch = staged;
-    *d_w = staged + 3 * TVM_NUM_CHALLENGES;
-    return TVM_OK;
-}
-struct QuotientSplit {
-    bool split, split4, split3, remainder;   // the gates in tvm_all_quotients_combined, where each is explained
-};
-static QuotientSplit quotient_split(const tvm_ctx* c, const tvm_table* mt, const tvm_table* at, tvm_domain td, tvm_domain qd);
-
-int32_t tvm_all_quotients_combined(tvm_ctx* c, const tvm_table* mt, const tvm_table* at, tvm_domain td,
-                                              tvm_domain qd, const uint64_t* h_challenges, const uint64_t* h_weights,
-                                              uint64_t* d_out) {
-    TVM_TRY(quotient_arguments(c, mt, at, td, qd, h_challenges, h_weights, d_out));
-    const u64 *d_ch = nullptr, *d_w = nullptr;
-    TVM_TRY(stage_quotient_inputs(c, h_challenges, h_weights, &d_ch, &d_w));
-    // Valid-trace mode (tvm_ctx_set_option TVM_OPTION_AIR_VALID_TRACE; off by default).  Every column is a polynomial with at most m = interpolant_len coefficients, every constraint has degree
-    // <= 4 in the columns (the AIR is degree-lowered to 4), so a constraint polynomial has degree <= 4(m - 1).  The
-    // consistency and transition quotients divide by X^N - 1 (the transition one times X - w^-1): fewer than
-    // 4(m - 1) + 2 - N coefficients -- about 3N + 4h, when the quotient domain has 8N points.  If that fits HALF the
-    // quotient domain, those constraints (87 % of the work) are evaluated on its even points only, interpolated there and
-    // evaluated on all points.  On a VALID trace -- the constraints vanish on the trace domain, so the quotients ARE
-    // polynomials -- these are exactly the field elements the row-by-row evaluation yields, at half the cost; on an
-    // invalid trace the row-by-row values are those of a rational function and differ (either way the unmodified
-    // verifier rejects: it recomputes the quotient at the out-of-domain point).  An initial / terminal quotient (zerofier of
-    // degree 1) has up to d(m - 1) coefficients for a constraint of degree d: the 100 of degree <= 3 fit the half domain too
-    // (3(m - 1) <= half) and are generated as a low-degree part; the FOUR of degree 4 are evaluated on every point.
-    // The constraints of lower degree have shorter quotients still (air_gen.h: TVM_AIR_PART_CLASS): those of class 2 -- a quarter
-    // of the multiplications -- have fewer than N + 2h coefficients and are evaluated on a QUARTER of the points, interpolated
-    // there, and their coefficients added to the half-domain interpolant before the one evaluation on all points.
-    // (a quotient domain short enough for the parts to run side by side is evaluated row by row: air.hip, fork lanes)
-    const u64 half = qd.length / 2, quarter = qd.length / 4;
-    const QuotientSplit gate = quotient_split(c, mt, at, td, qd);
-    const bool split4 = gate.split4, split3 = gate.split3;
-    if (!gate.split)
-        return all_quotients_combined(c, mt->data, mt->layout, (u64)mt->W, at->data, (u64)at->W, td.length, td.generator,
-                                      qd.offset, qd.generator, qd.length, d_ch, d_w, d_out);
-    // (class 2 on the quarter domain: transition quotients of degree-2 constraints have 2(m - 1) + 2 - N coefficients at most;
-    // class 3 on THREE cosets of the trace domain: those of degree-3 constraints have 3(m - 1) + 2 - N <= 3N)
-    const u64 N = td.length;
-    // One coset fewer per class, plus one block T of a sixth coset (quotients_by_remainder_coset, above): when every class's quotient
-    // has at most M = n1 coefficients beyond its whole blocks of N -- class 1 (parts 1-5) fewer than 3N + 4h, class 3 (6, 7) 2N + 3h,
-    // class 2 (8, 9) N + 2h -- and the trace is long enough that the dropped cosets (about 1.9 ms of AIR work at 2^18 rows, a quarter of
-    // that at 2^16) outweigh the latency of the three short evaluations on T (about 0.1 ms each, whatever N).
-    if (gate.remainder) return tvm::quotients_by_remainder_coset(c, mt, at, td, qd, d_ch, d_w, d_out);
-    PoolBlock low_block(c, (size_t)(2 * 3 * half + (split4 ? 2 * 3 * quarter : 0) + (split3 ? 6 * 3 * N : 0)) * sizeof(u64));  // released on every exit path
-    u64* low = (u64*)low_block.p;
-    if (!low) return set_error(c, TVM_ERR_OUT_OF_MEMORY, "quotient scratch");
-    u64* coeffs = low + 3 * half;
-    const tvm_domain half_dom = {qd.offset, bfe_mul(qd.generator, qd.generator), half};
-    const int CLASS_FULL = 1 << 0, CLASS_HALF = 1 << 1, CLASS_QUARTER = 1 << 2, CLASS_THREE = 1 << 3;
-    int rc = all_quotients_combined(c, mt->data, mt->layout, (u64)mt->W, at->data, (u64)at->W, td.length, td.generator,
-                                    half_dom.offset, half_dom.generator, half, d_ch, d_w, low,
-                                    CLASS_HALF | (split4 ? 0 : CLASS_QUARTER) | (split3 ? 0 : CLASS_THREE), 0);
-    if (rc == TVM_OK) rc = tvm_interpolate(c, 3, low, half_dom, coeffs);
-    u64* extra = coeffs + 3 * half;
-    if (rc == TVM_OK && split4) {
-        u64* low4 = extra;
-        u64* coeffs4 = low4 + 3 * quarter;
-        extra = coeffs4 + 3 * quarter;
-        const u64 g2 = bfe_mul(qd.generator, qd.generator);
-        const tvm_domain quarter_dom = {qd.offset, bfe_mul(g2, g2), quarter};
-        rc = all_quotients_combined(c, mt->data, mt->layout, (u64)mt->W, at->data, (u64)at->W, td.length, td.generator,
-                                    quarter_dom.offset, quarter_dom.generator, quarter, d_ch, d_w, low4, CLASS_QUARTER, 0);
-        if (rc == TVM_OK) rc = tvm_interpolate(c, 3, low4, quarter_dom, coeffs4);
-        if (rc == TVM_OK) rc = tvm_xfe_add_assign(c, coeffs, coeffs4, quarter);
-    }
-    if (rc == TVM_OK && split3) {
-        // P = A + X^N B + X^2N C with A, B, C of degree < N.  On the coset gamma_k <w_N> (gamma_k = offset * generator^k) X^N is the
-        // constant c_k = gamma_k^N, so P restricted to it is the polynomial Q_k = A + c_k B + c_k^2 C of degree < N: three cosets
-        // (k = 0, 2, 4: among the rows the tables hold for the half domain), three N-point interpolations, and the inverse of the
-        // 3 x 3 Vandermonde matrix of (c_0, c_2, c_4) coefficient by coefficient.
-        const u64 gN = bfe_mul(bfe_mul(bfe_mul(qd.generator, qd.generator), bfe_mul(qd.generator, qd.generator)),
-                               bfe_mul(bfe_mul(qd.generator, qd.generator), bfe_mul(qd.generator, qd.generator)));  // generator^8: order N
-        const u64 rows_per_table_coset = mt->layout.X / (qd.length / N);   // table cosets per quotient-domain coset (1 when the LDT domain is the quotient domain)
-        u64 cs[3];
-        u64* vals = extra;          // [3][N] XFE values, then [3][N] XFE coefficients
-        u64* qk = vals + 9 * N;
-        for (int j = 0; j < 3 && rc == TVM_OK; j++) {
-            const u64 k = 2 * (u64)j;
-            const u64 gamma = bfe_mul(qd.offset, bfe_pow(qd.generator, k));
-            cs[j] = bfe_pow(gamma, N);
-            const tvm_domain dom = {gamma, gN, N};
-            TabLayout lm = mt->layout;   // the one coset of the tables this domain is: a table of its own
-            lm.X = 1;
-            lm.log_x = 0;
-            const u64 first_row = k * rows_per_table_coset * mt->layout.pitch;
-            const u64* sub_main = mt->data + tvm_tab_idx(first_row, 0, (u64)mt->W);
-            const u64* sub_aux = at->data + tvm_tab_idx(first_row, 0, (u64)at->W);
-            rc = all_quotients_combined(c, sub_main, lm, (u64)mt->W, sub_aux, (u64)at->W, td.length, td.generator, dom.offset,
-                                        dom.generator, N, d_ch, d_w, vals + 3 * N * j, CLASS_THREE, 0);
-            if (rc == TVM_OK) rc = tvm_interpolate(c, 3, vals + 3 * N * j, dom, qk + 3 * N * j);
-        }
-        if (rc == TVM_OK) {
-            // inverse Vandermonde: row r of V^-1 holds the coefficients of the Lagrange basis polynomial data, i.e.
-            // [A B C]^T = V^-1 [Q_0 Q_2 Q_4]^T with V = [[1, c, c^2]]
-            tvm::ThreeCosetWeights w;
-            const u64 c0 = cs[0], c1 = cs[1], c2 = cs[2];
-            const u64 d0 = bfe_inv(bfe_mul(bfe_sub(c0, c1), bfe_sub(c0, c2)));
-            const u64 d1 = bfe_inv(bfe_mul(bfe_sub(c1, c0), bfe_sub(c1, c2)));
-            const u64 d2 = bfe_inv(bfe_mul(bfe_sub(c2, c0), bfe_sub(c2, c1)));
-            // Lagrange polynomial L_k(t) = prod_{j != k} (t - c_j) / prod (c_k - c_j) = (t^2 - (sum of the other two) t + product) * d_k
-            const u64 dk[3] = {d0, d1, d2};
-            const u64 oth[3][2] = {{c1, c2}, {c0, c2}, {c0, c1}};
-            for (int k3 = 0; k3 < 3; k3++) {
-                w.w[0 * 3 + k3] = bfe_mul(bfe_mul(oth[k3][0], oth[k3][1]), dk[k3]);             // t^0 -> A
-                w.w[1 * 3 + k3] = bfe_mul(bfe_neg(bfe_add(oth[k3][0], oth[k3][1])), dk[k3]);    // t^1 -> B
-                w.w[2 * 3 + k3] = dk[k3];                                                       // t^2 -> C
-            }
-            TVM_LAUNCH(tvm::k_three_coset_combine, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, c->stream, qk, qk + 3 * N, qk + 6 * N, N, w, coeffs);
-            TVM_HIP_CHECK(c, hipGetLastError());
-        }
-    }
-    if (rc == TVM_OK) rc = tvm_evaluate(c, 3, coeffs, half, qd, d_out);
-    if (rc == TVM_OK)
-        rc = all_quotients_combined(c, mt->data, mt->layout, (u64)mt->W, at->data, (u64)at->W, td.length, td.generator,
-                                    qd.offset, qd.generator, qd.length, d_ch, d_w, d_out, CLASS_FULL, 1);
-    return rc;
-}
-
-static QuotientSplit quotient_split(const tvm_ctx* c, const tvm_table* mt, const tvm_table* at, tvm_domain td, tvm_domain qd) {
-    const u64 m = mt->interpolant_len > at->interpolant_len ? mt->interpolant_len : at->interpolant_len;
-    const u64 half = qd.length / 2, quarter = qd.length / 4, N = td.length, M = mt->layout.n1;
-    QuotientSplit g;
-    g.split = c->air_valid_trace && !tvm::air_parts_fork(c, qd.length) && mt->interpolant_len && at->interpolant_len && half >= 2 * N && half % N == 0 &&
-              4 * (m - 1) + 2 <= half + N && 3 * (m - 1) <= half && mt->rows % half == 0;
-    g.split4 = g.split && quarter >= 2 * N && quarter % N == 0 && 2 * (m - 1) + 2 <= quarter + N && m <= quarter;
-    g.split3 = g.split4 && half == 4 * N && 3 * (m - 1) + 2 <= 4 * N && 2 * (m - 1) <= 3 * N && mt->layout.X == at->layout.X &&
-               mt->layout.pitch == at->layout.pitch && mt->layout.X == 2 * (half / N) && mt->layout.pitch % TVM_RB == 0;
-    g.remainder = g.split3 && c->air_remainder_coset && N >= c->air_remainder_min_rows && M % TVM_RB == 0 &&
-                  4 * (m - 1) + 1 <= 4 * N + M &&                                 // class 0 (the coefficient form only)
-                  4 * (m - 1) + 2 <= 4 * N + M && 3 * (m - 1) <= 3 * N + M &&     // class 1
-                  3 * (m - 1) + 2 <= 3 * N + M && 2 * (m - 1) <= 2 * N + M &&     // class 3
-                  2 * (m - 1) + 2 <= 2 * N + M && m <= N + M;                     // class 2
-    return g;
-}
-
-// The combined quotient in COEFFICIENT form, for a prover that goes on to the segments (tvm_quotient_segments_from_coefficients): no
-// codeword of the quotient domain is made and taken apart again.  Only where the remainder-coset gate above holds; elsewhere the
-// status is TVM_NOT_APPLICABLE, nothing is written and the caller takes tvm_all_quotients_combined.
-extern "C" int32_t tvm_all_quotients_coefficients(tvm_ctx* c, const tvm_table* mt, const tvm_table* at, tvm_domain td, tvm_domain qd,
-                                                  const uint64_t* h_challenges, const uint64_t* h_weights, uint64_t* d_coeffs,
-                                                  uint64_t capacity, uint64_t* n_coeffs) {
-    if (!n_coeffs) return set_error(c, TVM_ERR_INVALID_ARGUMENT, "all_quotients_coefficients arguments");
-    *n_coeffs = 0;
-    TVM_TRY(quotient_arguments(c, mt, at, td, qd, h_challenges, h_weights, d_coeffs));
-    if (!quotient_split(c, mt, at, td, qd).remainder) return TVM_NOT_APPLICABLE;
-    const u64 n = 4 * td.length + mt->layout.n1;
-    if (capacity < n) return set_error(c, TVM_ERR_INVALID_ARGUMENT, "all_quotients_coefficients: capacity below 4 N + n1 elements");
-    const u64 *d_ch = nullptr, *d_w = nullptr;
-    TVM_TRY(stage_quotient_inputs(c, h_challenges, h_weights, &d_ch, &d_w));
-    TVM_TRY(tvm::remainder_coset_coefficients(c, mt, at, td, qd, d_ch, d_w, true, d_coeffs));
-    *n_coeffs = n;
-    return TVM_OK;
-}
-
-// ---- the valid-trace AIR piecewise: what tvm_all_quotients_combined does in one call on one device, as the pieces a multi-GPU
-// host distributes over its ranks (triton_vm_amd/host/sharded_host.cpp).  A class's quotient polynomial has fewer than n * N
-// coefficients (n = tvm_air_class_cosets), so its values on ANY n cosets of the trace domain determine it.
-extern "C" {
-int32_t tvm_air_class_cosets(const tvm_table* mt, const tvm_table* at, tvm_domain td, uint32_t out[4]) {
-    if (!mt || !at || !out || !valid_domain(td)) return TVM_ERR_INVALID_ARGUMENT;
-    const u64 m = mt->interpolant_len > at->interpolant_len ? mt->interpolant_len : at->interpolant_len;
-    const u64 N = td.length;
-    out[0] = out[1] = out[2] = out[3] = 0;
-    if (!mt->interpolant_len || !at->interpolant_len) return TVM_OK;
-    // the bounds of tvm_all_quotients_combined (above): consistency / transition quotients of degree-d constraints have at most
-    // d (m - 1) + 2 - N coefficients, initial / terminal ones d' (m - 1) + 1 with d' one class lower
-    if (4 * (m - 1) + 2 <= 5 * N && 3 * (m - 1) <= 4 * N) out[1] = 4;   // class "half"
-    if (2 * (m - 1) + 2 <= 3 * N && m <= 2 * N) out[2] = 2;             // class "quarter"
-    if (3 * (m - 1) + 2 <= 4 * N && 2 * (m - 1) <= 3 * N) out[3] = 3;   // class "three cosets"
-    return TVM_OK;
-}
-
-int32_t tvm_air_class_values(tvm_ctx* c, const tvm_table* mt, const tvm_table* at, tvm_domain td, tvm_domain table_dom, uint32_t coset,
-                             uint32_t class_mask, const uint64_t* h_challenges, const uint64_t* h_weights, uint64_t* d_out) {
-    if (!c || !mt || !at || !h_challenges || !h_weights || !d_out || !valid_domain(td) || !valid_domain(table_dom) || !class_mask || class_mask > 15)
-        return set_error(c, TVM_ERR_INVALID_ARGUMENT, "air_class_values arguments");
-    const u64 N = td.length;
-    if (mt->fk != 1 || mt->n_cols != TVM_NUM_MAIN_COLUMNS || at->fk != 3 || at->n_cols != TVM_NUM_AUX_COLUMNS || mt->rows != at->rows ||
-        mt->rows != table_dom.length || table_dom.length % N || coset >= table_dom.length / N || !mt->has_successor_blocks ||
-        !at->has_successor_blocks || mt->layout.X != table_dom.length / N || at->layout.X != mt->layout.X || mt->layout.pitch != at->layout.pitch ||
-        mt->layout.pitch % TVM_RB)
-        return set_error(c, TVM_ERR_INVALID_ARGUMENT, "air_class_values: tables made by tvm_lde_table over table_domain, one coset of them");
-    u64* staged = (u64*)scratch(c, Scratch::QuotientInputs, (size_t)3 * (TVM_NUM_CHALLENGES + TVM_NUM_QUOTIENT_WEIGHTS) * sizeof(u64));
-    if (!staged) return set_error(c, TVM_ERR_OUT_OF_MEMORY, "challenge staging");
-    TVM_TRY(tvm::h2d_small(c, staged, h_challenges, 3 * TVM_NUM_CHALLENGES * sizeof(u64)));
-    TVM_TRY(tvm::h2d_small(c, staged + 3 * TVM_NUM_CHALLENGES, h_weights, 3 * TVM_NUM_QUOTIENT_WEIGHTS * sizeof(u64)));
-    const u64 X = table_dom.length / N;
-    const u64 gamma = bfe_mul(table_dom.offset, bfe_pow(table_dom.generator, coset));
-    TabLayout lm = mt->layout;   // the one coset of the tables: a table of its own (the layout is coset-major, context.h)
-    lm.X = 1;
-    lm.log_x = 0;
-    const u64 first_row = (u64)coset * mt->layout.pitch;
-    return all_quotients_combined(c, mt->data + tvm_tab_idx(first_row, 0, (u64)mt->W), lm, (u64)mt->W, at->data + tvm_tab_idx(first_row, 0, (u64)at->W),
-                                  (u64)at->W, N, td.generator, gamma, bfe_pow(table_dom.generator, X), N, staged, staged + 3 * TVM_NUM_CHALLENGES,
-                                  d_out, (int)class_mask, 0);
-}
-
-int32_t tvm_coset_values_to_coefficients(tvm_ctx* c, tvm_domain td, uint32_t n_cosets, const uint64_t* h_offsets,
-                                         const uint64_t* const* d_values, uint64_t* d_coeffs) {
-    if (!c || !valid_domain(td) || !n_cosets || n_cosets > 4 || !h_offsets || !d_values || !d_coeffs)
-        return set_error(c, TVM_ERR_INVALID_ARGUMENT, "coset_values_to_coefficients arguments");
-    const u64 N = td.length;
-    // P = sum_i X^(iN) A_i with A_i of degree < N.  On the coset gamma_j <w_N>, X^N is the constant c_j = gamma_j^N, so the
-    // interpolant of P's values there is Q_j = sum_i c_j^i A_i: n interpolations, then the inverse of the n x n Vandermonde
-    // matrix of (c_0 .. c_{n-1}) coefficient by coefficient.  Row i of the inverse holds the coefficients of x^i in the
-    // Lagrange basis polynomials L_j(x) = prod_{l != j} (x - c_l) / (c_j - c_l).
-    u64 cs[4];
-    for (uint32_t j = 0; j < n_cosets; j++) cs[j] = bfe_pow(h_offsets[j], N);
-    tvm::CosetCombineWeights w;
-    if (!tvm::coset_combine_weights(cs, n_cosets, w))
-        return set_error(c, TVM_ERR_INVALID_ARGUMENT, "coset_values_to_coefficients: two cosets with the same X^N");
-    PoolBlock block(c, (size_t)n_cosets * 3 * N * sizeof(u64));
-    u64* q = (u64*)block.p;
-    if (!q) return set_error(c, TVM_ERR_OUT_OF_MEMORY, "coset interpolants");
-    tvm::CosetCombinePointers ptrs;
-    for (uint32_t j = 0; j < 4; j++) ptrs.q[j] = nullptr;
-    for (uint32_t j = 0; j < n_cosets; j++) {
-        if (!d_values[j]) return set_error(c, TVM_ERR_INVALID_ARGUMENT, "coset_values_to_coefficients: null values");
-        const tvm_domain dom = {h_offsets[j], td.generator, N};
-        TVM_TRY(tvm_interpolate(c, 3, d_values[j], dom, q + (u64)j * 3 * N));
-        ptrs.q[j] = q + (u64)j * 3 * N;
-    }
-    TVM_LAUNCH(tvm::k_coset_combine, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, c->stream, ptrs, (int)n_cosets, N, w, d_coeffs, 1);
-    TVM_HIP_CHECK(c, hipGetLastError());
-    return TVM_OK;
-}
-}  // extern "C"
+// (tvm_all_quotients_combined / _coefficients and the routes of valid-trace mode -- what the tests' docstrings call
+// capi.hip: quotients_by_remainder_coset -- are in quotient.hip: remainder_coset_coefficients, chosen by quotient_plan.h)
 
 // ---------------------------------------------------------------------------------- STIR
 extern "C" {

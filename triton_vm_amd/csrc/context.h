@@ -104,7 +104,7 @@ namespace tvm {
 //   * unit slots: asked for inside a kernel unit (ntt.hip, air.hip, poly.hip, pad.hip) by a function that calls no other function
 //     that takes a slot -- the bottom; every caller above may rely on their being distinct from its own.
 // The cases that decide it:
-//   * tvm_all_quotients_combined / _coefficients and tvm_air_class_values hold QuotientInputs while air.hip takes ZerofierInverses
+//   * tvm_all_quotients_combined / _coefficients and tvm_air_class_values (quotient.hip) hold QuotientInputs while air.hip takes ZerofierInverses
 //     and AirAccumulators, and (valid-trace mode) while tvm_evaluate / tvm_interpolate take FoldedCoefficients and NttTemp;
 //   * tvm_quotient_segments holds QuotientCoefficients and SmallIn across quotient_segments_of_coefficients, which holds SegmentFolded
 //     and SegmentValues across ntt_columns (NttTemp); lde_table takes its intermediates from the pool;
@@ -183,7 +183,7 @@ struct tvm_ctx {
     std::map<void*, size_t> pool_live;                  // block -> capacity
     size_t pool_bytes = 0;                              // bytes held from the driver (live + cached)
     size_t pool_limit = 0;                              // tvm_ctx_set_memory_limit: 0 = whatever the device has
-    bool air_valid_trace = false;                       // TVM_OPTION_AIR_VALID_TRACE (capi.hip: tvm_all_quotients_combined)
+    bool air_valid_trace = false;                       // TVM_OPTION_AIR_VALID_TRACE (quotient_plan.h; quotient.hip)
     int lde_chunk_columns = 0;                          // TVM_OPTION_LDE_CHUNK_COLUMNS: 0 = chosen by lde_table (ntt.hip)
     int lde_pass2_tiles = 0;                            // TVM_OPTION_LDE_PASS2_TILES: 1 = the tile kernels instead of k_lde_pass2_fused (A/B)
     bool lde_pass2_scale_absorbed = true;               // TVM_OPTION_LDE_PASS2_SCALE_ABSORBED (ntt.hip: lde_table, k_lde_pass2_fused)
@@ -209,7 +209,7 @@ struct tvm_ctx {
     hipStream_t fork[3] = {};
     hipEvent_t fork_ready = nullptr, fork_done[3] = {};
     u64 air_fork_max_workgroups = 256;                  // TVM_OPTION_AIR_FORK_MAX_WORKGROUPS (0 after set_option(…, 0): never fork)
-    bool air_remainder_coset = true;                    // TVM_OPTION_AIR_REMAINDER_COSET (capi.hip: quotients_by_remainder_coset)
+    bool air_remainder_coset = true;                    // TVM_OPTION_AIR_REMAINDER_COSET (quotient_plan.h; quotient.hip)
     u64 air_remainder_min_rows = 1ull << 18;            // TVM_OPTION_AIR_REMAINDER_MIN_ROWS
     u64 air_check_chunk_rows = 1ull << 18;              // TVM_OPTION_AIR_CHECK_CHUNK_ROWS (air_check.hip: tvm_check_constraints)
 };

@@ -4,6 +4,8 @@
 #include "context.h"
 
 namespace tvm {
+// what every entry point asks of a domain it is given
+inline bool valid_domain(const tvm_domain& d) { return is_pow2(d.length) && d.generator < TVM_P && d.offset < TVM_P; }
 // ntt.hip
 int ntt_columns(tvm_ctx* c, const u64* in, u64 in_len, int in_fk, u64 in_col_stride, u64* out, int out_fk,
                 u64 out_col_stride, u64 out_mul, u64 out_add, int ncols, u64 n, u64 w, u64 in_scale, u64 out_scale,

@@ -259,8 +259,6 @@ int weight_vectors_launch(tvm_ctx* c, const u64* d_scalars, const u64* d_segment
     TVM_HIP_CHECK(c, hipGetLastError());
     return TVM_OK;
 }
-bool valid_domain(const tvm_domain& d) { return is_pow2(d.length) && d.generator < TVM_P && d.offset < TVM_P; }
-
 int deep_sum_device_args(tvm_ctx* c, int n_comp, const u64* const* d_cw, const u64* d_points, const u64* d_values, const u64* d_weights,
                          u64 offset, u64 gen, u64 n, u64* d_out) {
     DeepDeviceArgs a = {};
