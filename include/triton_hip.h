@@ -501,6 +501,58 @@ uint64_t tvm_out_of_domain_to_deep_block_words(uint64_t n_main_cols, uint64_t n_
  * sum_{1<=k<5} w1^k segments[k][1].  One launch, one synchronisation. */
 int32_t tvm_combination_weight_vectors(tvm_ctx* ctx, const uint64_t* h_scalars, const uint64_t* h_segments, uint32_t n_columns,
                                        uint64_t* h_w_columns, uint64_t* h_wp, uint64_t* h_wr, uint64_t* h_wd, uint64_t* h_pr_values);
+/* tvm_out_of_domain_to_deep with the sponge state in device memory, where the proof's front left it (TVM_FRONT_STATE of its block):
+ * d_sponge_state, 16 words, is read, and on return holds the state after the combination weights (what h_block carries at
+ * TVM_MIDDLE_STATE).  Everything else, the block and the one synchronisation included, as tvm_out_of_domain_to_deep. */
+int32_t tvm_out_of_domain_to_deep_device_state(tvm_ctx* ctx, const uint64_t* d_main_trace, uint64_t n_main_cols,
+                                               const uint64_t* d_main_randomizers, const uint64_t* d_aux_trace, uint64_t n_aux_cols,
+                                               const uint64_t* d_aux_randomizers, uint64_t n_rows, uint64_t num_trace_randomizers,
+                                               tvm_domain trace_domain, const uint64_t* d_polys, uint64_t poly_len, const tvm_table* segments,
+                                               const uint64_t* d_quotient_nodes, tvm_domain short_domain, uint64_t zeta,
+                                               uint64_t* d_sponge_state, uint64_t* d_combination, uint64_t* h_block, uint64_t block_capacity);
+
+/* ---- the PROOF FRONT: from the main table's Merkle root to the quotient weights (Prover::prove steps 5-10, stark.rs:369-401) with the
+ * transcript on the device, without the host in between (csrc/proof_front.hip) -------------------------------
+ * The front's state lives in a block of TVM_FRONT_BLOCK_WORDS words of device memory that the CALLER owns (tvm_malloc), because several
+ * entry points queue work on it in turn; the kernels that take challenges and weights from device memory (the _device_args entry points
+ * below) are pointed at its parts.  The long weight vector comes last: the first TVM_FRONT_HEAD_WORDS words are all a host replays. */
+#define TVM_FRONT_MAIN_ROOT 0u        /* [5] */
+#define TVM_FRONT_AUX_ROOT 5u         /* [5] */
+#define TVM_FRONT_CHALLENGES 10u      /* [63][3]: the 59 sampled challenges, then the terminals of input, output, lookup table, digest */
+#define TVM_FRONT_WEIGHT_SCALAR 199u  /* [3]: the scalar whose powers are the quotient weights */
+#define TVM_FRONT_STATE 202u          /* [16]: the sponge, after the last front call queued */
+#define TVM_FRONT_HEAD_WORDS 218u
+#define TVM_FRONT_WEIGHTS 218u        /* [604][3]: the scalar's powers 0 .. 603 */
+#define TVM_FRONT_BLOCK_WORDS 2030u
+/* Steps 5-6: h_sponge_state (16 words), the claim's program digest (5 words), public input and public output (Montgomery words, any
+ * length; null where the length is 0) are staged, then on the stream: ProofItem::MerkleRoot(d_main_nodes[1]) absorbed and handed out
+ * (TVM_FRONT_MAIN_ROOT), sample_scalars(59), and the four derived challenges of Challenges::new (challenges.rs:85-121) --
+ * EvalArg::compute_terminal of the input at challenge 1, the output at challenge 2, Tip5's lookup table at challenge 54 and the digest
+ * at challenge 0.  d_main_nodes: the main table's tree [2 L][5].  Does NOT synchronise; on bad arguments nothing is queued. */
+int32_t tvm_front_challenges(tvm_ctx* ctx, const uint64_t* d_main_nodes, const uint64_t* h_sponge_state, const uint64_t* h_program_digest,
+                             const uint64_t* h_input, uint64_t n_input, const uint64_t* h_output, uint64_t n_output, uint64_t* d_front);
+/* Steps 9-10: ProofItem::MerkleRoot(d_aux_nodes[1]) absorbed into the state in the block and handed out (TVM_FRONT_AUX_ROOT),
+ * sample_scalars(1) (TVM_FRONT_WEIGHT_SCALAR), its powers 0 .. 603 (TVM_FRONT_WEIGHTS).  Does NOT synchronise. */
+int32_t tvm_front_quotient_weights(tvm_ctx* ctx, const uint64_t* d_aux_nodes, uint64_t* d_front);
+/* Queues the download of the block's first n_words words (1 .. TVM_FRONT_BLOCK_WORDS) into h_block.  wait != 0: synchronises the
+ * stream.  wait == 0: h_block must stay alive, and its words are valid only after the context's next synchronisation (tvm_sync, or any
+ * entry point that synchronises). */
+int32_t tvm_front_block(tvm_ctx* ctx, const uint64_t* d_front, uint64_t* h_block, uint64_t n_words, uint32_t wait);
+uint64_t tvm_front_block_words(void);   /* TVM_FRONT_BLOCK_WORDS */
+/* The entry points that take challenges (63 XFE) and quotient weights (604 XFE) from HOST arrays, with those arrays in DEVICE memory
+ * instead, where earlier work of the stream may have left them (TVM_FRONT_CHALLENGES, TVM_FRONT_WEIGHTS of a front block): the same
+ * bodies without the staging copy -- nothing is copied, nothing waits.  The arrays are only read and must not be freed or overwritten
+ * before the work queued here has run. */
+int32_t tvm_extend_aux_table_device_args(tvm_ctx* ctx, const uint64_t* d_main_trace, uint64_t* d_aux_trace, uint64_t n_rows,
+                                         const uint64_t* d_challenges);
+int32_t tvm_fill_derived_aux_columns_device_args(tvm_ctx* ctx, const uint64_t* d_main_trace, uint64_t* d_aux_trace, uint64_t n_rows,
+                                                 const uint64_t* d_challenges);
+int32_t tvm_all_quotients_combined_device_args(tvm_ctx* ctx, const tvm_table* main_table, const tvm_table* aux_table,
+                                               tvm_domain trace_domain, tvm_domain quotient_domain, const uint64_t* d_challenges,
+                                               const uint64_t* d_weights, uint64_t* d_quotient_codeword);
+int32_t tvm_all_quotients_coefficients_device_args(tvm_ctx* ctx, const tvm_table* main_table, const tvm_table* aux_table,
+                                                   tvm_domain trace_domain, tvm_domain quotient_domain, const uint64_t* d_challenges,
+                                                   const uint64_t* d_weights, uint64_t* d_coeffs, uint64_t capacity, uint64_t* n_coeffs);
 
 /* ---- the PROOF TAIL: what follows the commit phase of Fri::prove (fri.rs:265-319) and the trace openings of Prover::prove
  * (stark.rs:665-716) with the transcript on the device (csrc/proof_tail.hip) ------------------------------------

@@ -133,6 +133,20 @@ _SIGNATURES = {
                                               C.c_uint64, Domain, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, Domain, C.c_uint64,
                                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]),
     "tvm_out_of_domain_to_deep_block_words": (C.c_uint64, [C.c_uint64, C.c_uint64]),
+    "tvm_out_of_domain_to_deep_device_state": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p,
+                                                           C.c_uint64, C.c_uint64, Domain, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, Domain,
+                                                           C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]),
+    "tvm_front_challenges": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64,
+                                         C.c_void_p]),
+    "tvm_front_quotient_weights": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "tvm_front_block": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32]),
+    "tvm_front_block_words": (C.c_uint64, []),
+    "tvm_extend_aux_table_device_args": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]),
+    "tvm_fill_derived_aux_columns_device_args": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]),
+    "tvm_all_quotients_combined_device_args": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, Domain, Domain, C.c_void_p, C.c_void_p,
+                                                           C.c_void_p]),
+    "tvm_all_quotients_coefficients_device_args": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, Domain, Domain, C.c_void_p, C.c_void_p,
+                                                               C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
     "tvm_combination_weight_vectors": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32] + [C.c_void_p] * 5),
     "tvm_fri_split_and_fold": (C.c_int32, [C.c_void_p, C.c_void_p, Domain, C.c_void_p, C.c_void_p]),
     "tvm_stir_merkle_tree": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p]),

@@ -752,14 +752,26 @@ int32_t tvm_fill_derived_main_columns(tvm_ctx* c, uint64_t* d_main_trace, uint64
     if (!c || !d_main_trace || n_rows < 2) return set_error(c, TVM_ERR_INVALID_ARGUMENT, "tvm_fill_derived_main_columns arguments");
     return fill_degree_lowering(c, 0, d_main_trace, nullptr, nullptr, n_rows);
 }
+// tvm_fill_derived_aux_columns and its _device_args twin: one body; `staged`: the challenges are a host array and go through the slot
+static int fill_derived_aux_columns(tvm_ctx* c, const uint64_t* d_main_trace, uint64_t* d_aux_trace, uint64_t n_rows, const uint64_t* challenges,
+                                    bool staged) {
+    if (!c || !d_main_trace || !d_aux_trace || !challenges || n_rows < 2)
+        return set_error(c, TVM_ERR_INVALID_ARGUMENT, "tvm_fill_derived_aux_columns arguments");
+    if (staged) {
+        u64* slot = (u64*)scratch(c, Scratch::FillChallenges, (size_t)3 * TVM_NUM_CHALLENGES * sizeof(u64));
+        if (!slot) return set_error(c, TVM_ERR_OUT_OF_MEMORY, "challenge staging");
+        TVM_TRY(tvm::h2d_small(c, slot, challenges, 3 * TVM_NUM_CHALLENGES * sizeof(u64)));   // (h_challenges may be a caller temporary)
+        challenges = slot;
+    }
+    return fill_degree_lowering(c, 1, const_cast<u64*>(d_main_trace), d_aux_trace, challenges, n_rows);
+}
 int32_t tvm_fill_derived_aux_columns(tvm_ctx* c, const uint64_t* d_main_trace, uint64_t* d_aux_trace, uint64_t n_rows,
                                      const uint64_t* h_challenges) {
-    if (!c || !d_main_trace || !d_aux_trace || !h_challenges || n_rows < 2)
-        return set_error(c, TVM_ERR_INVALID_ARGUMENT, "tvm_fill_derived_aux_columns arguments");
-    u64* staged = (u64*)scratch(c, Scratch::FillChallenges, (size_t)3 * TVM_NUM_CHALLENGES * sizeof(u64));
-    if (!staged) return set_error(c, TVM_ERR_OUT_OF_MEMORY, "challenge staging");
-    TVM_TRY(tvm::h2d_small(c, staged, h_challenges, 3 * TVM_NUM_CHALLENGES * sizeof(u64)));   // (h_challenges may be a caller temporary)
-    return fill_degree_lowering(c, 1, const_cast<u64*>(d_main_trace), d_aux_trace, staged, n_rows);
+    return fill_derived_aux_columns(c, d_main_trace, d_aux_trace, n_rows, h_challenges, true);
+}
+int32_t tvm_fill_derived_aux_columns_device_args(tvm_ctx* c, const uint64_t* d_main_trace, uint64_t* d_aux_trace, uint64_t n_rows,
+                                                 const uint64_t* d_challenges) {
+    return fill_derived_aux_columns(c, d_main_trace, d_aux_trace, n_rows, d_challenges, false);
 }
 
 int32_t tvm_fill_main_table(tvm_ctx* c, const tvm_aet* aet, uint64_t* d_main_trace, uint64_t n_rows, uint64_t* h_table_lengths_out) {
@@ -778,14 +790,26 @@ int32_t tvm_pad_main_table(tvm_ctx* c, uint64_t* d_main_trace, uint64_t n_rows, 
     return pad_main_table(c, d_main_trace, n_rows, h_table_lengths);
 }
 
+// tvm_extend_aux_table and its _device_args twin: one body (as fill_derived_aux_columns)
+static int extend_aux_table_entry(tvm_ctx* c, const uint64_t* d_main_trace, uint64_t* d_aux_trace, uint64_t n_rows, const uint64_t* challenges,
+                                  bool staged) {
+    if (!c || !d_main_trace || !d_aux_trace || !challenges || n_rows < 2)
+        return set_error(c, TVM_ERR_INVALID_ARGUMENT, "tvm_extend_aux_table arguments");
+    if (staged) {
+        u64* slot = (u64*)scratch(c, Scratch::ExtendChallenges, (size_t)3 * TVM_NUM_CHALLENGES * sizeof(u64));
+        if (!slot) return set_error(c, TVM_ERR_OUT_OF_MEMORY, "challenge staging");
+        TVM_TRY(tvm::h2d_small(c, slot, challenges, 3 * TVM_NUM_CHALLENGES * sizeof(u64)));   // (h_challenges may be a caller temporary)
+        challenges = slot;
+    }
+    return extend_aux_table(c, d_main_trace, d_aux_trace, challenges, n_rows);
+}
 int32_t tvm_extend_aux_table(tvm_ctx* c, const uint64_t* d_main_trace, uint64_t* d_aux_trace, uint64_t n_rows,
                              const uint64_t* h_challenges) {
-    if (!c || !d_main_trace || !d_aux_trace || !h_challenges || n_rows < 2)
-        return set_error(c, TVM_ERR_INVALID_ARGUMENT, "tvm_extend_aux_table arguments");
-    u64* staged = (u64*)scratch(c, Scratch::ExtendChallenges, (size_t)3 * TVM_NUM_CHALLENGES * sizeof(u64));
-    if (!staged) return set_error(c, TVM_ERR_OUT_OF_MEMORY, "challenge staging");
-    TVM_TRY(tvm::h2d_small(c, staged, h_challenges, 3 * TVM_NUM_CHALLENGES * sizeof(u64)));   // (h_challenges may be a caller temporary)
-    return extend_aux_table(c, d_main_trace, d_aux_trace, staged, n_rows);
+    return extend_aux_table_entry(c, d_main_trace, d_aux_trace, n_rows, h_challenges, true);
+}
+int32_t tvm_extend_aux_table_device_args(tvm_ctx* c, const uint64_t* d_main_trace, uint64_t* d_aux_trace, uint64_t n_rows,
+                                         const uint64_t* d_challenges) {
+    return extend_aux_table_entry(c, d_main_trace, d_aux_trace, n_rows, d_challenges, false);
 }
 
 // (tvm_all_quotients_combined / _coefficients and the routes of valid-trace mode -- what the tests' docstrings call

@@ -154,6 +154,7 @@ enum class Scratch : int {
     AirCheckPairs,          // ... and their words
     MiddleBlock,            // tvm_out_of_domain_to_deep: the block that goes back to the host and the weight vectors behind it, held
                             // across out_of_domain_rows, poly_eval, ntt_columns (unit slots) and tvm_evaluate (helper and unit slots)
+    FrontClaim,             // tvm_front_challenges: the claim's digest, input and output (it calls nothing that takes a slot)
     CombinationForm,        // tvm_evaluate_extended: the polynomial in coefficient form, its upper part behind it as the randomizers
     CombinationTable,       // ... and its values as a table of one column in the order of the last LDE pass
     Count

@@ -330,14 +330,16 @@ int32_t tvm_combination_weight_vectors(tvm_ctx* c, const uint64_t* h_scalars, co
 
 uint64_t tvm_out_of_domain_to_deep_block_words(uint64_t n_main_cols, uint64_t n_aux_cols) { return TVM_MIDDLE_BLOCK_WORDS(n_main_cols, n_aux_cols); }
 
-int32_t tvm_out_of_domain_to_deep(tvm_ctx* c, const uint64_t* d_main_trace, uint64_t n_main, const uint64_t* d_main_rnd,
-                                  const uint64_t* d_aux_trace, uint64_t n_aux, const uint64_t* d_aux_rnd, uint64_t n, uint64_t h,
-                                  tvm_domain td, const uint64_t* d_polys, uint64_t poly_len, const tvm_table* segments,
-                                  const uint64_t* d_quotient_nodes, tvm_domain sd, uint64_t zeta, const uint64_t* h_state,
-                                  uint64_t* d_combination, uint64_t* h_block, uint64_t block_capacity) {
+// tvm_out_of_domain_to_deep and its _device_state twin: one body.  The sponge state comes from the host (h_state, staged) or lies on the
+// device (d_state_io: copied into the block device to device, and the state after the combination weights copied back the same way).
+static int out_of_domain_to_deep(tvm_ctx* c, const uint64_t* d_main_trace, uint64_t n_main, const uint64_t* d_main_rnd,
+                                 const uint64_t* d_aux_trace, uint64_t n_aux, const uint64_t* d_aux_rnd, uint64_t n, uint64_t h,
+                                 tvm_domain td, const uint64_t* d_polys, uint64_t poly_len, const tvm_table* segments,
+                                 const uint64_t* d_quotient_nodes, tvm_domain sd, uint64_t zeta, const uint64_t* h_state, uint64_t* d_state_io,
+                                 uint64_t* d_combination, uint64_t* h_block, uint64_t block_capacity) {
     if (!c || !d_main_trace || !d_aux_trace || (h && (!d_main_rnd || !d_aux_rnd)) || !n_main || !n_aux || n_main + n_aux > (1u << 20) ||
         !valid_domain(td) || td.length != n || h > n || !d_polys || !poly_len || !segments || segments->fk != 3 || segments->n_cols != 5 ||
-        !valid_domain(sd) || sd.length > segments->rows || zeta >= TVM_P || !h_state || !d_combination || !h_block ||
+        !valid_domain(sd) || sd.length > segments->rows || zeta >= TVM_P || (!h_state && !d_state_io) || !d_combination || !h_block ||
         block_capacity < TVM_MIDDLE_BLOCK_WORDS(n_main, n_aux))
         return set_error(c, TVM_ERR_INVALID_ARGUMENT, "tvm_out_of_domain_to_deep arguments");
     if (td.offset != TVM_ONE) return set_error(c, TVM_ERR_UNSUPPORTED, "trace domain offset must be 1");
@@ -359,7 +361,8 @@ int32_t tvm_out_of_domain_to_deep(tvm_ctx* c, const uint64_t* d_main_trace, uint
         return rc;
     };
     auto queue = [&]() -> int {
-        TVM_TRY(h2d_small(c, d_state, h_state, 16 * sizeof(u64)));
+        if (d_state_io) TVM_HIP_CHECK(c, hipMemcpyAsync(d_state, d_state_io, 16 * sizeof(u64), hipMemcpyDeviceToDevice, c->stream));
+        else TVM_TRY(h2d_small(c, d_state, h_state, 16 * sizeof(u64)));
         // 12 (the root into the sponge), 13: the out-of-domain point, rows and segment values
         MiddlePointsArgs mp = {d_state, d_quotient_nodes, td.generator, zeta, d_root, d_points};
         TVM_LAUNCH(k_middle_points, dim3(1), dim3(64), 0, c->stream, mp);
@@ -379,9 +382,26 @@ int32_t tvm_out_of_domain_to_deep(tvm_ctx* c, const uint64_t* d_main_trace, uint
         // 16: DEEP
         const u64* cws[4] = {mac, mac, cw_p, cw_r};
         TVM_TRY(deep_sum_device_args(c, 4, cws, d_points, d_values, d_wd, sd.offset, sd.generator, S, d_combination));
+        if (d_state_io) TVM_HIP_CHECK(c, hipMemcpyAsync(d_state_io, d_state, 16 * sizeof(u64), hipMemcpyDeviceToDevice, c->stream));
         TVM_HIP_CHECK(c, hipMemcpyAsync(h_block, d, w_block * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
         return TVM_OK;
     };
     return leave(queue());
+}
+int32_t tvm_out_of_domain_to_deep(tvm_ctx* c, const uint64_t* d_main_trace, uint64_t n_main, const uint64_t* d_main_rnd,
+                                  const uint64_t* d_aux_trace, uint64_t n_aux, const uint64_t* d_aux_rnd, uint64_t n, uint64_t h,
+                                  tvm_domain td, const uint64_t* d_polys, uint64_t poly_len, const tvm_table* segments,
+                                  const uint64_t* d_quotient_nodes, tvm_domain sd, uint64_t zeta, const uint64_t* h_state,
+                                  uint64_t* d_combination, uint64_t* h_block, uint64_t block_capacity) {
+    return out_of_domain_to_deep(c, d_main_trace, n_main, d_main_rnd, d_aux_trace, n_aux, d_aux_rnd, n, h, td, d_polys, poly_len, segments,
+                                 d_quotient_nodes, sd, zeta, h_state, nullptr, d_combination, h_block, block_capacity);
+}
+int32_t tvm_out_of_domain_to_deep_device_state(tvm_ctx* c, const uint64_t* d_main_trace, uint64_t n_main, const uint64_t* d_main_rnd,
+                                               const uint64_t* d_aux_trace, uint64_t n_aux, const uint64_t* d_aux_rnd, uint64_t n, uint64_t h,
+                                               tvm_domain td, const uint64_t* d_polys, uint64_t poly_len, const tvm_table* segments,
+                                               const uint64_t* d_quotient_nodes, tvm_domain sd, uint64_t zeta, uint64_t* d_state,
+                                               uint64_t* d_combination, uint64_t* h_block, uint64_t block_capacity) {
+    return out_of_domain_to_deep(c, d_main_trace, n_main, d_main_rnd, d_aux_trace, n_aux, d_aux_rnd, n, h, td, d_polys, poly_len, segments,
+                                 d_quotient_nodes, sd, zeta, nullptr, d_state, d_combination, h_block, block_capacity);
 }
 }  // extern "C"

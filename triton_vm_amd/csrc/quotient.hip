@@ -284,26 +284,53 @@ static QuotientShape quotient_shape(const tvm_ctx* c, const tvm_table* mt, const
     return {td.length, qd.length, larger_interpolant(mt, at), l.n1, l.n2, l.pitch, l.X, mt->rows, c->air_valid_trace, air_parts_fork(c, qd.length),
             c->air_remainder_coset, c->air_remainder_min_rows};
 }
-static int stage_quotient_inputs(tvm_ctx* c, const uint64_t* h_challenges, const uint64_t* h_weights, const u64** d_ch, const u64** d_w) {
-    u64* staged = (u64*)scratch(c, Scratch::QuotientInputs, (size_t)3 * (TVM_NUM_CHALLENGES + TVM_NUM_QUOTIENT_WEIGHTS) * sizeof(u64));
-    if (!staged) return set_error(c, TVM_ERR_OUT_OF_MEMORY, "challenge staging");
-    TVM_TRY(h2d_small(c, staged, h_challenges, 3 * TVM_NUM_CHALLENGES * sizeof(u64)));
-    TVM_TRY(h2d_small(c, staged + 3 * TVM_NUM_CHALLENGES, h_weights, 3 * TVM_NUM_QUOTIENT_WEIGHTS * sizeof(u64)));
-    *d_ch = staged;
-    *d_w = staged + 3 * TVM_NUM_CHALLENGES;
+// `staged`: the two arrays are host arrays and go through the slot; else they are device arrays and are used where they lie
+static int stage_quotient_inputs(tvm_ctx* c, const uint64_t* challenges, const uint64_t* weights, bool staged, const u64** d_ch, const u64** d_w) {
+    *d_ch = challenges;
+    *d_w = weights;
+    if (!staged) return TVM_OK;
+    u64* slot = (u64*)scratch(c, Scratch::QuotientInputs, (size_t)3 * (TVM_NUM_CHALLENGES + TVM_NUM_QUOTIENT_WEIGHTS) * sizeof(u64));
+    if (!slot) return set_error(c, TVM_ERR_OUT_OF_MEMORY, "challenge staging");
+    TVM_TRY(h2d_small(c, slot, challenges, 3 * TVM_NUM_CHALLENGES * sizeof(u64)));
+    TVM_TRY(h2d_small(c, slot + 3 * TVM_NUM_CHALLENGES, weights, 3 * TVM_NUM_QUOTIENT_WEIGHTS * sizeof(u64)));
+    *d_ch = slot;
+    *d_w = slot + 3 * TVM_NUM_CHALLENGES;
     return TVM_OK;
 }
-extern "C" {
-int32_t tvm_all_quotients_combined(tvm_ctx* c, const tvm_table* mt, const tvm_table* at, tvm_domain td, tvm_domain qd,
-                                   const uint64_t* h_challenges, const uint64_t* h_weights, uint64_t* d_out) {
-    TVM_TRY(quotient_arguments(c, mt, at, td, qd, h_challenges, h_weights, d_out));
+// the bodies of the two entry points and of their _device_args twins
+static int quotients_combined(tvm_ctx* c, const tvm_table* mt, const tvm_table* at, tvm_domain td, tvm_domain qd, const uint64_t* challenges,
+                              const uint64_t* weights, bool staged, uint64_t* d_out) {
+    TVM_TRY(quotient_arguments(c, mt, at, td, qd, challenges, weights, d_out));
     const u64 *d_ch = nullptr, *d_w = nullptr;
-    TVM_TRY(stage_quotient_inputs(c, h_challenges, h_weights, &d_ch, &d_w));
+    TVM_TRY(stage_quotient_inputs(c, challenges, weights, staged, &d_ch, &d_w));
     const QuotientPlan plan = quotient_plan(quotient_shape(c, mt, at, td, qd));
     if (plan.route == QuotientRoute::row_by_row)
         return all_quotients_combined(c, mt->data, mt->layout, (u64)mt->W, at->data, (u64)at->W, td.length, td.generator, qd.offset,
                                       qd.generator, qd.length, d_ch, d_w, d_out);
     return quotients_by_class(c, mt, at, td, qd, d_ch, d_w, plan, d_out);
+}
+static int quotients_coefficients(tvm_ctx* c, const tvm_table* mt, const tvm_table* at, tvm_domain td, tvm_domain qd, const uint64_t* challenges,
+                                  const uint64_t* weights, bool staged, uint64_t* d_coeffs, uint64_t capacity, uint64_t* n_coeffs) {
+    if (!n_coeffs) return set_error(c, TVM_ERR_INVALID_ARGUMENT, "all_quotients_coefficients arguments");
+    *n_coeffs = 0;
+    TVM_TRY(quotient_arguments(c, mt, at, td, qd, challenges, weights, d_coeffs));
+    const QuotientPlan plan = quotient_plan(quotient_shape(c, mt, at, td, qd), true);
+    if (plan.route != QuotientRoute::remainder_coset) return TVM_NOT_APPLICABLE;
+    if (capacity < plan.n_coeffs) return set_error(c, TVM_ERR_INVALID_ARGUMENT, "all_quotients_coefficients: capacity below 4 N + n1 elements");
+    const u64 *d_ch = nullptr, *d_w = nullptr;
+    TVM_TRY(stage_quotient_inputs(c, challenges, weights, staged, &d_ch, &d_w));
+    TVM_TRY(remainder_coset_coefficients(c, mt, at, td, qd, d_ch, d_w, plan, d_coeffs));
+    *n_coeffs = plan.n_coeffs;
+    return TVM_OK;
+}
+extern "C" {
+int32_t tvm_all_quotients_combined(tvm_ctx* c, const tvm_table* mt, const tvm_table* at, tvm_domain td, tvm_domain qd,
+                                   const uint64_t* h_challenges, const uint64_t* h_weights, uint64_t* d_out) {
+    return quotients_combined(c, mt, at, td, qd, h_challenges, h_weights, true, d_out);
+}
+int32_t tvm_all_quotients_combined_device_args(tvm_ctx* c, const tvm_table* mt, const tvm_table* at, tvm_domain td, tvm_domain qd,
+                                               const uint64_t* d_challenges, const uint64_t* d_weights, uint64_t* d_out) {
+    return quotients_combined(c, mt, at, td, qd, d_challenges, d_weights, false, d_out);
 }
 // The combined quotient in COEFFICIENT form, for a prover that goes on to the segments (tvm_quotient_segments_from_coefficients): no
 // codeword of the quotient domain is made and taken apart again.  Only on the remainder route; elsewhere the status is
@@ -311,17 +338,12 @@ int32_t tvm_all_quotients_combined(tvm_ctx* c, const tvm_table* mt, const tvm_ta
 int32_t tvm_all_quotients_coefficients(tvm_ctx* c, const tvm_table* mt, const tvm_table* at, tvm_domain td, tvm_domain qd,
                                        const uint64_t* h_challenges, const uint64_t* h_weights, uint64_t* d_coeffs, uint64_t capacity,
                                        uint64_t* n_coeffs) {
-    if (!n_coeffs) return set_error(c, TVM_ERR_INVALID_ARGUMENT, "all_quotients_coefficients arguments");
-    *n_coeffs = 0;
-    TVM_TRY(quotient_arguments(c, mt, at, td, qd, h_challenges, h_weights, d_coeffs));
-    const QuotientPlan plan = quotient_plan(quotient_shape(c, mt, at, td, qd), true);
-    if (plan.route != QuotientRoute::remainder_coset) return TVM_NOT_APPLICABLE;
-    if (capacity < plan.n_coeffs) return set_error(c, TVM_ERR_INVALID_ARGUMENT, "all_quotients_coefficients: capacity below 4 N + n1 elements");
-    const u64 *d_ch = nullptr, *d_w = nullptr;
-    TVM_TRY(stage_quotient_inputs(c, h_challenges, h_weights, &d_ch, &d_w));
-    TVM_TRY(remainder_coset_coefficients(c, mt, at, td, qd, d_ch, d_w, plan, d_coeffs));
-    *n_coeffs = plan.n_coeffs;
-    return TVM_OK;
+    return quotients_coefficients(c, mt, at, td, qd, h_challenges, h_weights, true, d_coeffs, capacity, n_coeffs);
+}
+int32_t tvm_all_quotients_coefficients_device_args(tvm_ctx* c, const tvm_table* mt, const tvm_table* at, tvm_domain td, tvm_domain qd,
+                                                   const uint64_t* d_challenges, const uint64_t* d_weights, uint64_t* d_coeffs,
+                                                   uint64_t capacity, uint64_t* n_coeffs) {
+    return quotients_coefficients(c, mt, at, td, qd, d_challenges, d_weights, false, d_coeffs, capacity, n_coeffs);
 }
 // ---- the valid-trace AIR piecewise: what tvm_all_quotients_combined does in one call on one device, as the pieces a multi-GPU
 // host distributes over its ranks (triton_vm_amd/host/sharded_host.cpp).  A class's quotient polynomial has fewer than n * N
@@ -344,7 +366,7 @@ int32_t tvm_air_class_values(tvm_ctx* c, const tvm_table* mt, const tvm_table* a
         mt->layout.pitch % TVM_RB)
         return set_error(c, TVM_ERR_INVALID_ARGUMENT, "air_class_values: tables made by tvm_lde_table over table_domain, one coset of them");
     const u64 *d_ch = nullptr, *d_w = nullptr;
-    TVM_TRY(stage_quotient_inputs(c, h_challenges, h_weights, &d_ch, &d_w));
+    TVM_TRY(stage_quotient_inputs(c, h_challenges, h_weights, true, &d_ch, &d_w));
     const u64 gamma = bfe_mul(table_dom.offset, bfe_pow(table_dom.generator, coset));
     const TableCoset t = table_coset(mt, at, coset);
     return all_quotients_combined(c, t.main, t.layout, (u64)mt->W, t.aux, (u64)at->W, N, td.generator, gamma,

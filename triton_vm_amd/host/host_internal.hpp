@@ -78,6 +78,8 @@ public:
           assume_valid_trace(assume_valid_trace_) {}
     virtual ~ProofSteps() {}
     ProofStream prove();
+    // `extend` with the 63 challenges in device memory (TVMH_OPTION_DEVICE_FRONT); a prover that sets `extend` alone keeps the host's front
+    std::function<void(const u64*)> extend_device;
 
 protected:
     struct Openings {   // of the three tables, by Which
@@ -115,6 +117,10 @@ protected:
     // 10: the quotient -> the segment table on this rank's LDT rows (the caller frees it) and the five segment polynomials
     virtual tvm_table* quotient_segments(const std::vector<Xfe>& challenges, const std::vector<Xfe>& weights, u64 zeta, DeviceBuffer& polys,
                                          u64 poly_len) = 0;
+    // ... with the challenges and the weights in device memory (TVMH_OPTION_DEVICE_FRONT); only a prover with whole_trees_here() is asked
+    virtual tvm_table* quotient_segments(const u64* /*d_challenges*/, const u64* /*d_weights*/, u64 /*zeta*/, DeviceBuffer& /*polys*/, u64 /*poly_len*/) {
+        throw Error(TVM_ERR_UNSUPPORTED, "quotient_segments from device arrays: the single-GPU prover only");
+    }
     virtual Words out_of_domain_rows(const MasterTable& mt, const std::vector<Xfe>& points) { return mt.out_of_domain_rows(points); }
     // 15: the weighted sums wp, wr of the segments on this rank's rows of the short domain: rows of the segment table
     virtual void segment_combinations(const tvm_table* segments, const DeviceBuffer& polys, u64 poly_len, const ArithmeticDomain& short_rank,
@@ -138,6 +144,11 @@ protected:
     // TVMH_OPTION_DEVICE_MIDDLE: commit(QUOT, ..) without fetching the root, where this prover has the whole traces and builds the whole
     // quotient tree (the single-GPU one) -> the tree's nodes on the device; null, and nothing done: the proof's middle keeps the host's path
     virtual const u64* commit_whole_quotient_tree(const tvm_table* /*segments*/) { return nullptr; }
+    // TVMH_OPTION_DEVICE_FRONT: commit(MAIN / AUX, ..) without fetching the root, where this prover builds the whole tree over the whole
+    // extended table (the single-GPU one) -> the tree's nodes on the device; null, and nothing done: the proof's front keeps the host's
+    // path.  whole_trees_here() says which it will be before anything is extended.
+    virtual const u64* commit_whole_tree(Which /*w*/) { return nullptr; }
+    virtual bool whole_trees_here() const { return false; }
 
 private:
     std::vector<u64> fri(DeviceBuffer&& combination);   // -> the first-round indices
@@ -145,8 +156,15 @@ private:
     // 13-16 on this rank's rows of the short domain -> the DEEP codeword; a4: the point alpha^4, which step 18 checks.  host_middle: the
     // host in the loop; device_middle: the quotient root and 13-16 in one device round trip (false: does not apply, nothing was done)
     DeviceBuffer host_middle(const tvm_table* segments, const DeviceBuffer& polys, u64 poly_len, const ArithmeticDomain& short_rank, u64 zeta, Xfe& a4);
+    // d_front: the block of a device_front whose download and replay are still owed -- the middle starts from the block's sponge state,
+    // and its one synchronisation serves both (the front is replayed before the middle's items are enqueued)
     bool device_middle(const tvm_table* segments, const DeviceBuffer& polys, u64 poly_len, const ArithmeticDomain& short_dom, u64 zeta, Xfe& a4,
-                       DeviceBuffer& combination);
+                       DeviceBuffer& combination, u64* d_front);
+    // 4-10 queued without a wait, the sponge on the device -> the front's block (its download and replay_front are owed), the segment
+    // table (the caller frees it) and the segment polynomials; false: does not apply, nothing was queued or enqueued
+    bool device_front(u64 zeta, u64 poly_len, DeviceBuffer& front, tvm_table*& segments, DeviceBuffer& polys);
+    void fetch_front(const u64* d_front, std::vector<u64>& head, bool wait);
+    void replay_front(const std::vector<u64>& head);
     Openings tail_openings;   // the openings of step 19 when fri_device_tail has fetched them
     bool have_tail_openings = false;
 };

@@ -711,16 +711,28 @@ static std::atomic<uint64_t> g_device_middle_proofs{0};   // tvmh_device_middle_
 // three weights and the same state.  false: the call does not apply (no whole tables and whole quotient tree here: the sharded and
 // coset-wise provers) and nothing was enqueued or committed.
 bool ProofSteps::device_middle(const tvm_table* segments, const DeviceBuffer& polys, u64 poly_len, const ArithmeticDomain& short_dom, u64 zeta, Xfe& a4,
-                               DeviceBuffer& combination) {
+                               DeviceBuffer& combination, u64* d_front) {
     const u64* tree = commit_whole_quotient_tree(segments);
     if (!tree) return false;
     mark("out-of-domain rows to DEEP");
     const u64 n_main = main.n_cols(), n_aux = aux.n_cols();
     std::vector<u64> block(TVM_MIDDLE_BLOCK_WORDS(n_main, n_aux));
     combination = DeviceBuffer(c, short_dom.length * 3);
-    c.check(tvm_out_of_domain_to_deep(c.raw(), main.trace(), n_main, main.randomizers(), aux.trace(), n_aux, aux.randomizers(), p.trace.length, p.h,
-                                      p.trace.c(), polys.ptr(), poly_len, segments, tree, short_dom.c(), zeta, ps.sponge_state(), combination.ptr(),
-                                      block.data(), block.size()), "tvm_out_of_domain_to_deep");
+    if (d_front) {   // the front's words come back with this call's synchronisation; the sponge goes from the one to the other on the device
+        std::vector<u64> head;
+        fetch_front(d_front, head, false);
+        const int32_t status = tvm_out_of_domain_to_deep_device_state(c.raw(), main.trace(), n_main, main.randomizers(), aux.trace(), n_aux,
+                                                                      aux.randomizers(), p.trace.length, p.h, p.trace.c(), polys.ptr(), poly_len, segments,
+                                                                      tree, short_dom.c(), zeta, d_front + TVM_FRONT_STATE, combination.ptr(),
+                                                                      block.data(), block.size());
+        if (status != TVM_OK) (void)tvm_sync(c.raw());   // (a refusal queues nothing and waits for nothing: `head` is still being written)
+        c.check(status, "tvm_out_of_domain_to_deep_device_state");
+        replay_front(head);
+    } else {
+        c.check(tvm_out_of_domain_to_deep(c.raw(), main.trace(), n_main, main.randomizers(), aux.trace(), n_aux, aux.randomizers(), p.trace.length,
+                                          p.h, p.trace.c(), polys.ptr(), poly_len, segments, tree, short_dom.c(), zeta, ps.sponge_state(),
+                                          combination.ptr(), block.data(), block.size()), "tvm_out_of_domain_to_deep");
+    }
     const u64 *b = block.data(), *points = b + TVM_MIDDLE_POINTS, *rows_main = b + TVM_MIDDLE_MAIN_ROWS, *rows_aux = b + TVM_MIDDLE_AUX_ROWS(n_main),
               *seg = b + TVM_MIDDLE_SEGMENTS(n_main, n_aux);
     auto agree = [](bool same, const char* what) {
@@ -748,6 +760,57 @@ bool ProofSteps::device_middle(const tvm_table* segments, const DeviceBuffer& po
     return true;
 }
 
+static std::atomic<uint64_t> g_device_front_proofs{0};   // tvmh_device_front_proofs
+// TVMH_OPTION_DEVICE_FRONT: steps 4-10 queued without a wait -- main LDE, main tree, the main root into the sponge and the 63 challenges
+// (tvm_front_challenges), extend, aux LDE, aux tree, the aux root into the sponge and the 604 quotient weights
+// (tvm_front_quotient_weights), the quotient and the segments -- with challenges and weights read where the device left them.  The
+// download of the block's head and replay_front are owed afterwards.  false: the call does not apply (no whole trees on one GPU: the
+// sharded and coset-wise provers; `extend` without `extend_device`; TVMH_OPTION_CHECK_TRACE, which needs the challenges on the host
+// and decides the AIR's mode there) and nothing was queued or enqueued.
+bool ProofSteps::device_front(u64 zeta, u64 poly_len, DeviceBuffer& front, tvm_table*& segments, DeviceBuffer& polys) {
+    if (!whole_trees_here() || (extend && !extend_device) || tvmh_get_option(TVMH_OPTION_CHECK_TRACE)) return false;
+    front = DeviceBuffer(c, TVM_FRONT_BLOCK_WORDS);
+    u64* d = front.ptr();
+    mark("main LDE");
+    extend_master_table(MAIN);
+    mark("main Merkle");
+    const u64* main_tree = commit_whole_tree(MAIN);
+    if (!main_tree) throw Error(TVM_ERR_DEVICE, "device_front: no whole main tree");
+    c.check(tvm_front_challenges(c.raw(), main_tree, ps.sponge_state(), claim.program_digest, claim.input.data(), claim.input.size(),
+                                 claim.output.data(), claim.output.size(), d), "tvm_front_challenges");
+    mark("extend");
+    if (extend_device) extend_device(d + TVM_FRONT_CHALLENGES);
+    mark("aux LDE");
+    extend_master_table(AUX);
+    mark("aux Merkle");
+    const u64* aux_tree = commit_whole_tree(AUX);
+    if (!aux_tree) throw Error(TVM_ERR_DEVICE, "device_front: no whole aux tree");
+    c.check(tvm_front_quotient_weights(c.raw(), aux_tree, d), "tvm_front_quotient_weights");
+    mark("AIR quotients");
+    segments = quotient_segments(d + TVM_FRONT_CHALLENGES, d + TVM_FRONT_WEIGHTS, zeta, polys, poly_len);
+    return true;
+}
+void ProofSteps::fetch_front(const u64* d_front, std::vector<u64>& head, bool wait) {
+    head.resize(TVM_FRONT_HEAD_WORDS);
+    c.check(tvm_front_block(c.raw(), d_front, head.data(), head.size(), wait ? 1 : 0), "tvm_front_block");
+}
+// The host's side of device_front, once the head of the block is here: the two roots are enqueued from it and both samplings replayed
+// on this host's sponge, which must arrive at the same 63 challenges, the same weight scalar and the same state.
+void ProofSteps::replay_front(const std::vector<u64>& head) {
+    const u64* b = head.data();
+    auto agree = [](bool same, const char* what) {
+        if (!same) throw Error(TVM_ERR_DEVICE, std::string("the device's Fiat-Shamir sponge and the host's disagree on ") + what);
+    };
+    ps.enqueue("main root", b + TVM_FRONT_MAIN_ROOT, 5);
+    const std::vector<Xfe> challenges = derive_challenges(ps.sample_scalars(NUM_SAMPLED_CHALLENGES), claim);
+    agree(std::memcmp(challenges[0].c, b + TVM_FRONT_CHALLENGES, 3 * TVM_NUM_CHALLENGES * sizeof(u64)) == 0, "the challenges");
+    ps.enqueue("aux root", b + TVM_FRONT_AUX_ROOT, 5);
+    const Xfe w = ps.sample_scalars(1)[0];
+    agree(std::memcmp(w.c, b + TVM_FRONT_WEIGHT_SCALAR, 3 * sizeof(u64)) == 0, "the scalar of the quotient weights");
+    agree(std::memcmp(ps.sponge_state(), b + TVM_FRONT_STATE, 16 * sizeof(u64)) == 0, "the state after the quotient weights");
+    g_device_front_proofs++;
+}
+
 ProofStream ProofSteps::prove() {
     ps.alter_fiat_shamir_state_with(claim.encode());  // stark.rs:336-339
     {
@@ -759,35 +822,47 @@ ProofStream ProofSteps::prove() {
     const ArithmeticDomain ldt_rank = local(p.ldt), short_rank = local(short_dom);   // (one rank: the domains themselves)
     const u64 zeta = to_mont(3);  // Stark::ZETA, stark.rs:1801
 
-    // 4-6: main table LDE, Merkle tree, challenges  (stark.rs:367-377)
-    mark("main LDE");
-    extend_master_table(MAIN);
-    mark("main Merkle");
-    ps.enqueue("main root", commit(MAIN, nullptr).data(), 5);
-    const std::vector<Xfe> challenges = derive_challenges(ps.sample_scalars(NUM_SAMPLED_CHALLENGES), claim);
-    mark("extend");
-    if (extend) extend(challenges);  // MasterMainTable::extend (stark.rs:379-381); over ranks: replicated
-
-    // 8-9: aux table (its `extend` is host work in the reference; the trace is already resident)
-    mark("aux LDE");
-    extend_master_table(AUX);
-    mark("aux Merkle");
-    ps.enqueue("aux root", commit(AUX, nullptr).data(), 5);
-    const std::vector<Xfe> quotient_weights = xfe_powers(ps.sample_scalars(1)[0], 0, TVM_NUM_QUOTIENT_WEIGHTS);
-
-    // 10: quotient, segments, randomization  (stark.rs:405-423).  The quotient codeword is not part of the proof.
-    mark("AIR quotients");
     const u64 poly_len = std::max<u64>(p.quotient.length / 4, quotient_randomizer.size());
-    DeviceBuffer polys;
-    const TableGuard seg{c, quotient_segments(challenges, quotient_weights, zeta, polys, poly_len)};
+    DeviceBuffer polys, front;
+    tvm_table* segment_table = nullptr;
+    const bool fronted = tvmh_get_option(TVMH_OPTION_DEVICE_FRONT) && device_front(zeta, poly_len, front, segment_table, polys);
+    if (!fronted) {
+        // 4-6: main table LDE, Merkle tree, challenges  (stark.rs:367-377)
+        mark("main LDE");
+        extend_master_table(MAIN);
+        mark("main Merkle");
+        ps.enqueue("main root", commit(MAIN, nullptr).data(), 5);
+        const std::vector<Xfe> challenges = derive_challenges(ps.sample_scalars(NUM_SAMPLED_CHALLENGES), claim);
+        mark("extend");
+        if (extend) extend(challenges);  // MasterMainTable::extend (stark.rs:379-381); over ranks: replicated
+
+        // 8-9: aux table (its `extend` is host work in the reference; the trace is already resident)
+        mark("aux LDE");
+        extend_master_table(AUX);
+        mark("aux Merkle");
+        ps.enqueue("aux root", commit(AUX, nullptr).data(), 5);
+        const std::vector<Xfe> quotient_weights = xfe_powers(ps.sample_scalars(1)[0], 0, TVM_NUM_QUOTIENT_WEIGHTS);
+
+        // 10: quotient, segments, randomization  (stark.rs:405-423).  The quotient codeword is not part of the proof.
+        mark("AIR quotients");
+        segment_table = quotient_segments(challenges, quotient_weights, zeta, polys, poly_len);
+    }
+    const TableGuard seg{c, segment_table};
     // 12: quotient Merkle tree  (stark.rs:425-446); 13-16: out-of-domain rows, linear combinations, DEEP  (stark.rs:450-639)
     mark("quotient Merkle");
     Xfe a4;
     DeviceBuffer combination;
-    if (!(tvmh_get_option(TVMH_OPTION_DEVICE_MIDDLE) && device_middle(seg.t, polys, poly_len, short_rank, zeta, a4, combination))) {
+    if (!(tvmh_get_option(TVMH_OPTION_DEVICE_MIDDLE) &&
+          device_middle(seg.t, polys, poly_len, short_rank, zeta, a4, combination, fronted ? front.ptr() : nullptr))) {
+        if (fronted) {   // the front alone: its own round trip
+            std::vector<u64> head;
+            fetch_front(front.ptr(), head, true);
+            replay_front(head);
+        }
         ps.enqueue("quot root", commit(QUOT, seg.t).data(), 5);
         combination = host_middle(seg.t, polys, poly_len, short_rank, zeta, a4);
     }
+    front.reset();
     if (short_dom.length != L) {  // stark.rs:629-639: the quotient domain was the short one -- extend to the LDT domain
         const DeviceBuffer whole = gather_rows(std::move(combination), short_rank.length, 3, "combination codeword (short domain)");
         const DeviceBuffer coeffs = p.quotient.interpolate(c, whole.ptr(), 3);
@@ -864,6 +939,11 @@ struct WholeSteps : ProofSteps {
         build_tree(QUOT, segments);
         return nodes[QUOT].ptr();
     }
+    bool whole_trees_here() const override { return true; }
+    const u64* commit_whole_tree(Which w) override {
+        build_tree(w, nullptr);
+        return nodes[w].ptr();
+    }
     void build_tree(Which w, const tvm_table* segments) {
         if (w == QUOT) segment_table = segments;
         nodes[w] = DeviceBuffer(c, 10 * p.ldt.length);
@@ -873,15 +953,23 @@ struct WholeSteps : ProofSteps {
     // only elsewhere (exact mode, short traces, other expansion factors) a codeword is made and interpolated.
     tvm_table* quotient_segments(const std::vector<Xfe>& challenges, const std::vector<Xfe>& weights, u64 zeta, DeviceBuffer& polys,
                                  u64 poly_len) override {
+        return quotient_segments_of(challenges[0].c, weights[0].c, false, zeta, polys, poly_len);
+    }
+    tvm_table* quotient_segments(const u64* d_challenges, const u64* d_weights, u64 zeta, DeviceBuffer& polys, u64 poly_len) override {
+        return quotient_segments_of(d_challenges, d_weights, true, zeta, polys, poly_len);
+    }
+    // (on_device: the two arrays lie in device memory and go to the _device_args twins of the two quotient entry points)
+    tvm_table* quotient_segments_of(const u64* challenges, const u64* weights, bool on_device, u64 zeta, DeviceBuffer& polys, u64 poly_len) {
+        const auto coefficients = on_device ? tvm_all_quotients_coefficients_device_args : tvm_all_quotients_coefficients;
+        const auto combined = on_device ? tvm_all_quotients_combined_device_args : tvm_all_quotients_combined;
         DeviceBuffer quot(c, p.quotient.length * 3);
         if (assume_valid_trace) c.check(tvm_ctx_set_option(c.raw(), TVM_OPTION_AIR_VALID_TRACE, 1), "tvm_ctx_set_option");
         u64 n_coeffs = 0;
-        int32_t status = tvm_all_quotients_coefficients(c.raw(), main.table(), aux.table(), p.trace.c(), p.quotient.c(), challenges[0].c,
-                                                        weights[0].c, quot.ptr(), p.quotient.length, &n_coeffs);
+        int32_t status = coefficients(c.raw(), main.table(), aux.table(), p.trace.c(), p.quotient.c(), challenges, weights, quot.ptr(),
+                                      p.quotient.length, &n_coeffs);
         const bool from_coefficients = status == TVM_OK;
         if (status == TVM_NOT_APPLICABLE)
-            status = tvm_all_quotients_combined(c.raw(), main.table(), aux.table(), p.trace.c(), p.quotient.c(), challenges[0].c, weights[0].c,
-                                                quot.ptr());
+            status = combined(c.raw(), main.table(), aux.table(), p.trace.c(), p.quotient.c(), challenges, weights, quot.ptr());
         if (assume_valid_trace) (void)tvm_ctx_set_option(c.raw(), TVM_OPTION_AIR_VALID_TRACE, 0);
         c.check(status, from_coefficients ? "tvm_all_quotients_coefficients" : "tvm_all_quotients_combined");
         polys = DeviceBuffer(c, 5 * poly_len * 3);
@@ -923,7 +1011,11 @@ struct WholeSteps : ProofSteps {
 };
 }  // namespace
 
-ProofStream Prover::prove() { return WholeSteps(c_, p_, claim_, main_, aux_, quotient_randomizer_, extend, assume_valid_trace).prove(); }
+ProofStream Prover::prove() {
+    WholeSteps steps(c_, p_, claim_, main_, aux_, quotient_randomizer_, extend, assume_valid_trace);
+    steps.extend_device = extend_device;
+    return steps.prove();
+}
 
 // ------------------------------------------------------------------------------------------------ STIR
 namespace {
@@ -1305,6 +1397,12 @@ void ExecutionTables::extend(const Context& c, u64 n, const std::vector<Xfe>& ch
     c.check(tvm_fill_derived_aux_columns(c.raw(), main_trace.ptr(), aux_trace.ptr(), n, challenges[0].c), "tvm_fill_derived_aux_columns");
 }
 
+void ExecutionTables::extend(const Context& c, u64 n, const u64* d_challenges) const {
+    c.check(tvm_extend_aux_table_device_args(c.raw(), main_trace.ptr(), aux_trace.ptr(), n, d_challenges), "tvm_extend_aux_table_device_args");
+    c.check(tvm_fill_derived_aux_columns_device_args(c.raw(), main_trace.ptr(), aux_trace.ptr(), n, d_challenges),
+            "tvm_fill_derived_aux_columns_device_args");
+}
+
 TraceCheck check_trace(const Context& c, const u64* d_main_trace, const u64* d_aux_trace, u64 n_rows, const std::vector<Xfe>& challenges,
                        const uint8_t seed[32], u64 capacity) {
     TraceCheck r;
@@ -1340,6 +1438,8 @@ std::vector<u64> prove_execution(const Context& c, const StarkParameters& p, con
             std::fprintf(stderr, "[tvmh] constraint check: %llu failing rows (the first: row %llu, constraint %llu): exact AIR\n",
                          (unsigned long long)r.failing_rows, (unsigned long long)r.failures[0], (unsigned long long)r.failures[1]);
     };
+    // (the check needs the challenges on the host and decides the AIR's mode there: a checked proof keeps the host's front)
+    if (!check) prover.extend_device = [&](const u64* d_challenges) { t.extend(c, n, d_challenges); };
     const ProofStream stream = prover.prove();
     watch.lap("prove (extend + hot path)");
     std::vector<u64> proof = stream.proof();
@@ -1349,15 +1449,16 @@ std::vector<u64> prove_execution(const Context& c, const StarkParameters& p, con
 
 }  // namespace triton_vm
 
-static std::atomic<uint64_t> g_options[9] = {{0}, {0}, {0}, {0}, {0}, {0}, {0}, {0}, {0}};   // indexed by TVMH_OPTION_*
+static std::atomic<uint64_t> g_options[10] = {{0}, {0}, {0}, {0}, {0}, {0}, {0}, {0}, {0}, {0}};   // indexed by TVMH_OPTION_*
 extern "C" void tvmh_set_option(uint32_t option, uint64_t value) {
-    if (option >= 1 && option <= 8) g_options[option].store(value);
+    if (option >= 1 && option <= 9) g_options[option].store(value);
 }
-extern "C" uint64_t tvmh_get_option(uint32_t option) { return option >= 1 && option <= 8 ? g_options[option].load() : 0; }
+extern "C" uint64_t tvmh_get_option(uint32_t option) { return option >= 1 && option <= 9 ? g_options[option].load() : 0; }
 
 extern "C" uint64_t tvmh_device_tail_proofs(void) { return triton_vm::g_device_tail_proofs.load(); }
 extern "C" uint64_t tvmh_device_stir_proofs(void) { return triton_vm::g_device_stir_proofs.load(); }
 extern "C" uint64_t tvmh_device_middle_proofs(void) { return triton_vm::g_device_middle_proofs.load(); }
+extern "C" uint64_t tvmh_device_front_proofs(void) { return triton_vm::g_device_front_proofs.load(); }
 
 extern "C" int32_t tvmh_prove(tvm_ctx* ctx, uint32_t log2_padded_height, uint64_t num_trace_randomizers,
                               uint64_t num_collinearity_checks, uint32_t log2_expansion, const uint64_t* d_main_trace,

@@ -201,6 +201,9 @@ public:
     // called with the 63 challenges before the auxiliary table is extended: MasterMainTable::extend for a prover that
     // starts from an execution trace (prove_execution); the auxiliary trace buffer is filled then
     std::function<void(const std::vector<Xfe>&)> extend;
+    // the same with the 63 challenges in DEVICE memory ([63][3] words, read only; nothing may wait for the stream): what
+    // TVMH_OPTION_DEVICE_FRONT calls in place of `extend`.  A prover with `extend` set and this one not keeps the host's front.
+    std::function<void(const u64*)> extend_device;
     bool assume_valid_trace = false;  // TVM_OPTION_AIR_VALID_TRACE around the quotient evaluation
 
 private:
@@ -235,6 +238,7 @@ struct ExecutionTables {
     void fill_trace(const Context& c, u64 n_rows, u64 padded_height, const tvm_aet& aet, const uint8_t seed[32],
                     const std::function<void(const char*)>& lap);
     void extend(const Context& c, u64 n_rows, const std::vector<Xfe>& challenges) const;
+    void extend(const Context& c, u64 n_rows, const u64* d_challenges) const;   // the challenges in device memory: nothing is copied or waits
 };
 
 // tvm_check_constraints on a complete trace: the number of failing rows and (row, constraint index) pairs of the lowest of them
@@ -546,6 +550,26 @@ extern "C" uint64_t tvmh_device_stir_proofs(void);
 #define TVMH_OPTION_DEVICE_MIDDLE 8
 // how many proofs of this process took that path so far (a proof it does not apply to is not counted)
 extern "C" uint64_t tvmh_device_middle_proofs(void);
+// TVMH_OPTION_DEVICE_FRONT != 0: a single-GPU proof (FRI or STIR) queues steps 4-10 of Prover::prove without a wait -- main LDE and tree, the
+// main root into the sponge, the 59 sampled and 4 derived challenges (tvm_front_challenges), extend, aux LDE and tree, the aux root into
+// the sponge and the 604 quotient weights (tvm_front_quotient_weights), the quotient and the segments, whose kernels read challenges and
+// weights where the device left them (the _device_args entry points); the host fetches the head of the front's block
+// (tvm_front_block), enqueues the two roots from it, replays both samplings on its own sponge and throws TVM_ERR_DEVICE when a
+// challenge, the weight scalar or the state differs.  The same proof, word for word.  Default 0.  Keeps the host's path whatever the
+// value: the sharded and coset-wise provers (no whole trees on one GPU), a prover with `extend` set and `extend_device` not, and
+// TVMH_OPTION_CHECK_TRACE (the check needs the challenges on the host and decides the AIR's mode there; the option is looked at, not
+// whether a check will run, so it also keeps the host's path for tvmh_prove, which checks nothing: conservative, the same proof).  With
+// TVMH_OPTION_DEVICE_MIDDLE the sponge state passes from the front to the middle on the device
+// (tvm_out_of_domain_to_deep_device_state) and the middle's one synchronisation serves both.  Stream synchronisations of steps 4-16,
+// counted from the code (a warm context; TVMH_OPTION_TRACE = 1 adds one per stage):
+//     neither 7 (main root, aux root; quotient root, two out-of-domain row calls, segment values, combination values)
+//     FRONT   6 (tvm_front_block; the middle's five)            MIDDLE  3 (main root, aux root; the middle's one)            both  1
+// No wait hides in the LDEs, the trees, extend, the quotient or the segments.  What can wait inside h2d_small, on either path: an
+// array above a quarter of the staging ring (a public input or output of more than 2^17 words in tvm_front_challenges) is copied and
+// waited for, and the ring's wrap -- once in some tens of proofs -- drains the stream; a scratch slot that grows does too.
+#define TVMH_OPTION_DEVICE_FRONT 9
+// how many proofs of this process took that path so far (a proof it does not apply to is not counted)
+extern "C" uint64_t tvmh_device_front_proofs(void);
 extern "C" void tvmh_set_option(uint32_t option, uint64_t value);
 extern "C" uint64_t tvmh_get_option(uint32_t option);
 

@@ -55,6 +55,8 @@ def load_host_library(backend_path=None, out=None):
     lib.tvmh_device_stir_proofs.argtypes = []
     lib.tvmh_device_middle_proofs.restype = C.c_uint64
     lib.tvmh_device_middle_proofs.argtypes = []
+    lib.tvmh_device_front_proofs.restype = C.c_uint64
+    lib.tvmh_device_front_proofs.argtypes = []
     lib.tvmh_local_comms_create.restype = C.c_int32
     lib.tvmh_local_comms_create.argtypes = [C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)]
     lib.tvmh_local_comms_destroy.restype = None
@@ -74,6 +76,7 @@ OPTION_CHECK_TRACE = 5   # prove_execution checks the AIR on the trace first and
 OPTION_DEVICE_TAIL = 6   # single-GPU FRI proofs: the query phase and the trace openings in one device round trip (proof_tail.py)
 OPTION_DEVICE_STIR = 7   # Stir::prove: all rounds in one call with the sponge on the device (stir_rounds.py)
 OPTION_DEVICE_MIDDLE = 8   # single-GPU proofs: the quotient root, the out-of-domain rows, the combinations and DEEP in one device round trip (proof_middle.py)
+OPTION_DEVICE_FRONT = 9    # single-GPU proofs: main root to the segment table queued without a wait, challenges and quotient weights made on the device (proof_front.py)
 
 
 class host_option:
