@@ -1,6 +1,8 @@
-// host_internal.hpp -- what the translation units of the C++ host share (triton_host.cpp, sharded_host.cpp, verifier.cpp): helpers,
-// the steps of one proof (ProofSteps), the frame of an extern "C" entry point.  Not part of the interface: triton_host.hpp is.
+// host_internal.hpp -- what the translation units of the C++ host share (triton_host.cpp, device_transcript.cpp, sharded_host.cpp,
+// verifier.cpp): helpers, the steps of one proof (ProofSteps), the frame of an extern "C" entry point.  Not part of the interface:
+// triton_host.hpp is.
 #pragma once
+#include <algorithm>
 #include <cstdio>
 #include <cstring>
 #include <string>
@@ -24,6 +26,14 @@ std::vector<u64> auth_node_indices(u64 n_leaves, const std::vector<u64>& indices
 std::vector<Xfe> derive_challenges(std::vector<Xfe> sampled, const Claim& claim);  // Challenges::new (challenges.rs:85-121)
 std::vector<u64> trace_randomizers_host(const uint8_t table_seed[32], u64 n_cols, u64 h, int fk);
 DeviceBuffer upload(const Context& c, const std::vector<u64>& host);
+// Stir::prove and Stir::prove_on_device: stir.rs:404-412, and .map(|i| i % len).unique()
+static const int LOG2_DOMAIN_SHRINKAGE = 1;
+static inline std::vector<u64> unique_folded(const std::vector<u64>& indices, u64 folded_len) {
+    std::vector<u64> out;
+    for (u64 i : indices)
+        if (std::find(out.begin(), out.end(), i % folded_len) == out.end()) out.push_back(i % folded_len);
+    return out;
+}
 
 // Many gathers with one round trip (tvm_gather_elements_batch): jobs are queued with their index lists, run() fills `out`.
 struct GatherBatch {
@@ -64,8 +74,28 @@ struct TableGuard {
     ~TableGuard() { if (t) tvm_table_free(c.raw(), t); }
 };
 
+// The host's sponge replaying what the device's did (device_transcript.cpp, ProofSteps::fri): a sampling on `ps`, compared with the
+// words the device sampled.  One throw for every site.
+struct Replay {
+    ProofStream& ps;
+    static void agree(bool same, const char* what) {
+        if (!same) throw Error(TVM_ERR_DEVICE, std::string("the device's Fiat-Shamir sponge and the host's disagree on ") + what);
+    }
+    std::vector<Xfe> scalars(u64 n, const u64* device_words, const char* what) {   // (n = 0 compares nothing)
+        std::vector<Xfe> mine = ps.sample_scalars(n);
+        agree(n == 0 || std::memcmp(mine[0].c, device_words, n * sizeof(Xfe)) == 0, what);
+        return mine;
+    }
+    std::vector<u64> indices(u64 upper_bound, u64 n, const u64* device_indices, const char* what) {
+        std::vector<u64> mine = ps.sample_indices(upper_bound, n);
+        agree(n == 0 || std::memcmp(mine.data(), device_indices, n * sizeof(u64)) == 0, what);
+        return mine;
+    }
+    void state(const u64 device_state[16], const char* what) { agree(std::memcmp(ps.sponge_state(), device_state, 16 * sizeof(u64)) == 0, what); }
+};
+
 // One proof.  prove() is the statement sequence of Prover::prove (stark.rs:331-719) and fri() that of Fri::prove (fri.rs:212-319),
-// each written once (triton_host.cpp); the virtual steps are the ones that depend on where the data lies -- whole on one GPU
+// each written once (triton_host.cpp; the stretches with the sponge on the device: device_transcript.cpp); the virtual steps are the ones that depend on where the data lies -- whole on one GPU
 // (Prover, triton_host.cpp) or by cosets over ranks and passes (ShardedRun, sharded_host.cpp).  The hooks of
 // triton_vm_amd/prover.py are the model.  A step's default is the single-GPU one where that is a line.
 class ProofSteps {
@@ -84,6 +114,10 @@ public:
 protected:
     struct Openings {   // of the three tables, by Which
         Words rows[3], auth[3];
+    };
+    struct WholeTables {                  // the single-GPU prover's, by Which
+        const tvm_table* table[3] = {};   // MAIN, AUX: master(w).table(); QUOT: the segment table -- each as its commit saw it
+        DeviceBuffer nodes[3];            // the three whole Merkle trees [2 L][5]
     };
     struct FriRound {
         ArithmeticDomain dom;
@@ -117,7 +151,7 @@ protected:
     // 10: the quotient -> the segment table on this rank's LDT rows (the caller frees it) and the five segment polynomials
     virtual tvm_table* quotient_segments(const std::vector<Xfe>& challenges, const std::vector<Xfe>& weights, u64 zeta, DeviceBuffer& polys,
                                          u64 poly_len) = 0;
-    // ... with the challenges and the weights in device memory (TVMH_OPTION_DEVICE_FRONT); only a prover with whole_trees_here() is asked
+    // ... with the challenges and the weights in device memory (TVMH_OPTION_DEVICE_FRONT); only a prover with whole() is asked
     virtual tvm_table* quotient_segments(const u64* /*d_challenges*/, const u64* /*d_weights*/, u64 /*zeta*/, DeviceBuffer& /*polys*/, u64 /*poly_len*/) {
         throw Error(TVM_ERR_UNSUPPORTED, "quotient_segments from device arrays: the single-GPU prover only");
     }
@@ -138,17 +172,11 @@ protected:
     virtual std::vector<FriAnswer> answer_distributed(const std::vector<FriQuery>& /*queries*/) { return {}; }
     // 19: the rows of the three tables at `indices` and the authentication structures of the three trees
     virtual Openings open(const tvm_table* segments, const std::vector<u64>& indices) = 0;
-    // TVMH_OPTION_DEVICE_TAIL: the three tables (main, aux, quotient segments) extended over the whole LDT domain and their whole
-    // trees, where this prover has them (the single-GPU one); false: the proof's tail keeps the host's path
-    virtual bool whole_tables_and_trees(const tvm_table* /*tables*/[3], const u64* /*trees*/[3]) { return false; }
-    // TVMH_OPTION_DEVICE_MIDDLE: commit(QUOT, ..) without fetching the root, where this prover has the whole traces and builds the whole
-    // quotient tree (the single-GPU one) -> the tree's nodes on the device; null, and nothing done: the proof's middle keeps the host's path
-    virtual const u64* commit_whole_quotient_tree(const tvm_table* /*segments*/) { return nullptr; }
-    // TVMH_OPTION_DEVICE_FRONT: commit(MAIN / AUX, ..) without fetching the root, where this prover builds the whole tree over the whole
-    // extended table (the single-GPU one) -> the tree's nodes on the device; null, and nothing done: the proof's front keeps the host's
-    // path.  whole_trees_here() says which it will be before anything is extended.
-    virtual const u64* commit_whole_tree(Which /*w*/) { return nullptr; }
-    virtual bool whole_trees_here() const { return false; }
+    // TVMH_OPTION_DEVICE_FRONT / _MIDDLE / _TAIL: the whole tables and whole trees, where this prover holds them on one GPU (the single-GPU
+    // one); null (the sharded and coset-wise provers): those stretches of the proof keep the host's path
+    virtual WholeTables* whole() { return nullptr; }
+    // commit(w, ..) of a prover with whole(), the root left on the device (no round trip) -> the tree's nodes
+    const u64* build_whole_tree(Which w, const tvm_table* segments);
 
 private:
     std::vector<u64> fri(DeviceBuffer&& combination);   // -> the first-round indices

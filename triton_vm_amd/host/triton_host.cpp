@@ -523,9 +523,7 @@ std::vector<u64> ProofSteps::fri(DeviceBuffer&& combination) {
             rounds[first + k].cw = k == 0 ? cw : d_cw[k - 1];
             ps.enqueue("fri root " + std::to_string(first + k), &roots[5 * k], 5);
             if (k == left) break;
-            const Xfe challenge = ps.sample_scalars(1)[0];
-            if (std::memcmp(challenge.c, &challenges[3 * k], 3 * sizeof(u64)) != 0)
-                throw Error(TVM_ERR_DEVICE, "the device's Fiat-Shamir sponge and the host's disagree on a FRI folding challenge");
+            Replay{ps}.scalars(1, &challenges[3 * k], "a FRI folding challenge");
         }
         cw = rounds.back().cw;
         dom = rounds.back().dom;
@@ -580,51 +578,12 @@ std::vector<u64> ProofSteps::fri(DeviceBuffer&& combination) {
     return a_indices;
 }
 
-static std::atomic<uint64_t> g_device_tail_proofs{0};   // tvmh_device_tail_proofs
-// TVMH_OPTION_DEVICE_TAIL: everything of Fri::prove behind the commit phase (fri.rs:265-319) and the trace openings of step 19 in one
-// call, the sponge on the device (tvm_fri_query_and_open) -- then the two enqueues and the sampling are replayed on this host's sponge,
-// which must arrive at the same indices and the same state.  false: the call does not apply (no whole tables and trees here, more
-// checks than TVM_TAIL_MAX_INDICES) and nothing was enqueued.
-bool ProofSteps::fri_device_tail(const std::vector<FriRound>& rounds, std::vector<u64>& a_indices) {
-    const tvm_table* tables[3];
-    const u64* table_nodes[3];
-    if (!whole_tables_and_trees(tables, table_nodes)) return false;
-    const uint32_t n_rounds = (uint32_t)rounds.size() - 1, n_items = TVM_TAIL_ITEMS(n_rounds);
-    const u64 n_last = rounds.back().dom.length, q = p.num_collinearity_checks;
-    std::vector<const u64*> d_cw, d_nodes;
-    for (size_t r = 0; r < rounds.size(); r++) {
-        if (r) d_cw.push_back(rounds[r].cw);
-        d_nodes.push_back(rounds[r].nodes.ptr());
-    }
-    u64 state[16], n_payload = 0;
-    std::vector<u64> indices(q), last(3 * n_last), last_poly(3 * n_last), directory(2 * (size_t)n_items);
-    // (room for the bound -- every list n_checks full paths, some MB at 2^20 rows -- but not filled: only the pages the proof's words reach are touched)
-    const u64 capacity = tvm_fri_query_and_open_payload_bound(rounds[0].dom.c(), n_rounds, q, tables);
-    const std::unique_ptr<u64[]> payload(new u64[capacity ? capacity : 1]);
-    const int32_t status = tvm_fri_query_and_open(c.raw(), ps.sponge_state(), rounds[0].cw, rounds[0].dom.c(), n_rounds, d_cw.data(), d_nodes.data(), q,
-                                                  tables, table_nodes, p.ldt.length, state, indices.data(), last.data(), last_poly.data(),
-                                                  directory.data(), payload.get(), capacity, &n_payload);
-    if (status == TVM_NOT_APPLICABLE) return false;
-    c.check(status, "tvm_fri_query_and_open");
-    ps.enqueue("fri last codeword", last.data(), last.size());
-    ps.enqueue("fri last polynomial", last_poly.data(), last_poly.size());
-    a_indices = ps.sample_indices(p.ldt.length, q);
-    if (a_indices != indices || std::memcmp(state, ps.sponge_state(), sizeof(state)) != 0)
-        throw Error(TVM_ERR_DEVICE, "the device's Fiat-Shamir sponge and the host's disagree on the FRI query indices");
-    auto item = [&](size_t k) { return std::make_pair(payload.get() + directory[2 * k], directory[2 * k + 1]); };
-    for (size_t k = 0; 2 * k + 6 < n_items; k++) {   // round 0 at the a indices, then rounds 0 .. n_rounds - 1 at the b indices
-        const std::string round = std::to_string(k ? k - 1 : 0);
-        ps.enqueue("fri response " + round, item(2 * k).first, item(2 * k).second);
-        ps.enqueue("fri auth " + round, item(2 * k + 1).first, item(2 * k + 1).second);
-    }
-    for (int w = 0; w < 3; w++) {   // kept for step 19
-        const size_t k = n_items - 6 + 2 * (size_t)w;
-        tail_openings.rows[w].assign(item(k).first, item(k).first + item(k).second);
-        tail_openings.auth[w].assign(item(k + 1).first, item(k + 1).first + item(k + 1).second);
-    }
-    have_tail_openings = true;
-    g_device_tail_proofs++;
-    return true;
+const u64* ProofSteps::build_whole_tree(Which w, const tvm_table* segments) {
+    WholeTables& t = *whole();
+    t.table[w] = w == QUOT ? segments : master(w).table();
+    t.nodes[w] = DeviceBuffer(c, 10 * p.ldt.length);
+    c.check(tvm_table_merkle_tree(c.raw(), t.table[w], p.ldt.length, t.nodes[w].ptr()), "tvm_table_merkle_tree");
+    return t.nodes[w].ptr();
 }
 
 void ProofSteps::segment_combinations(const tvm_table* segments, const DeviceBuffer&, u64, const ArithmeticDomain& short_rank, const Xfe* wp,
@@ -702,113 +661,6 @@ DeviceBuffer ProofSteps::host_middle(const tvm_table* segments, const DeviceBuff
     cw_r.reset();
     comb.reset();
     return combination;
-}
-
-static std::atomic<uint64_t> g_device_middle_proofs{0};   // tvmh_device_middle_proofs
-// TVMH_OPTION_DEVICE_MIDDLE: the quotient root into the sponge and steps 13-16 in one call, the sponge on the device
-// (tvm_out_of_domain_to_deep: one stream synchronisation instead of five) -- then the root and the six out-of-domain items are enqueued
-// from the block that came back and both samplings are replayed on this host's sponge, which must arrive at the same alpha, the same
-// three weights and the same state.  false: the call does not apply (no whole tables and whole quotient tree here: the sharded and
-// coset-wise provers) and nothing was enqueued or committed.
-bool ProofSteps::device_middle(const tvm_table* segments, const DeviceBuffer& polys, u64 poly_len, const ArithmeticDomain& short_dom, u64 zeta, Xfe& a4,
-                               DeviceBuffer& combination, u64* d_front) {
-    const u64* tree = commit_whole_quotient_tree(segments);
-    if (!tree) return false;
-    mark("out-of-domain rows to DEEP");
-    const u64 n_main = main.n_cols(), n_aux = aux.n_cols();
-    std::vector<u64> block(TVM_MIDDLE_BLOCK_WORDS(n_main, n_aux));
-    combination = DeviceBuffer(c, short_dom.length * 3);
-    if (d_front) {   // the front's words come back with this call's synchronisation; the sponge goes from the one to the other on the device
-        std::vector<u64> head;
-        fetch_front(d_front, head, false);
-        const int32_t status = tvm_out_of_domain_to_deep_device_state(c.raw(), main.trace(), n_main, main.randomizers(), aux.trace(), n_aux,
-                                                                      aux.randomizers(), p.trace.length, p.h, p.trace.c(), polys.ptr(), poly_len, segments,
-                                                                      tree, short_dom.c(), zeta, d_front + TVM_FRONT_STATE, combination.ptr(),
-                                                                      block.data(), block.size());
-        if (status != TVM_OK) (void)tvm_sync(c.raw());   // (a refusal queues nothing and waits for nothing: `head` is still being written)
-        c.check(status, "tvm_out_of_domain_to_deep_device_state");
-        replay_front(head);
-    } else {
-        c.check(tvm_out_of_domain_to_deep(c.raw(), main.trace(), n_main, main.randomizers(), aux.trace(), n_aux, aux.randomizers(), p.trace.length,
-                                          p.h, p.trace.c(), polys.ptr(), poly_len, segments, tree, short_dom.c(), zeta, ps.sponge_state(),
-                                          combination.ptr(), block.data(), block.size()), "tvm_out_of_domain_to_deep");
-    }
-    const u64 *b = block.data(), *points = b + TVM_MIDDLE_POINTS, *rows_main = b + TVM_MIDDLE_MAIN_ROWS, *rows_aux = b + TVM_MIDDLE_AUX_ROWS(n_main),
-              *seg = b + TVM_MIDDLE_SEGMENTS(n_main, n_aux);
-    auto agree = [](bool same, const char* what) {
-        if (!same) throw Error(TVM_ERR_DEVICE, std::string("the device's Fiat-Shamir sponge and the host's disagree on ") + what);
-    };
-    ps.enqueue("quot root", b + TVM_MIDDLE_ROOT, 5);
-    const Xfe alpha = ps.sample_scalars(1)[0];
-    agree(std::memcmp(alpha.c, points, 3 * sizeof(u64)) == 0, "the out-of-domain point");
-    ps.enqueue("ood main", rows_main, n_main * 3);
-    ps.enqueue("ood aux", rows_aux, n_aux * 3);
-    ps.enqueue("ood main next", rows_main + n_main * 3, n_main * 3);
-    ps.enqueue("ood aux next", rows_aux + n_aux * 3, n_aux * 3);
-    u64 quot_p[12], quot_r[12];   // segments 0..3 at alpha^4, 1..4 at (zeta alpha)^4, out of [5][2][3]
-    for (int k = 0; k < 4; k++) {
-        std::memcpy(quot_p + 3 * k, seg + 3 * (2 * k), 3 * sizeof(u64));
-        std::memcpy(quot_r + 3 * k, seg + 3 * (2 * (k + 1) + 1), 3 * sizeof(u64));
-    }
-    ps.enqueue("ood quot p", quot_p, 12);
-    ps.enqueue("ood quot r", quot_r, 12);
-    const std::vector<Xfe> w3 = ps.sample_scalars(3);
-    agree(std::memcmp(w3[0].c, b + TVM_MIDDLE_WEIGHTS(n_main, n_aux), 9 * sizeof(u64)) == 0, "the combination weights");
-    agree(std::memcmp(ps.sponge_state(), b + TVM_MIDDLE_STATE(n_main, n_aux), 16 * sizeof(u64)) == 0, "the state after the combination weights");
-    std::memcpy(a4.c, points + 6, 3 * sizeof(u64));   // step 18 checks it against the revealed points
-    g_device_middle_proofs++;
-    return true;
-}
-
-static std::atomic<uint64_t> g_device_front_proofs{0};   // tvmh_device_front_proofs
-// TVMH_OPTION_DEVICE_FRONT: steps 4-10 queued without a wait -- main LDE, main tree, the main root into the sponge and the 63 challenges
-// (tvm_front_challenges), extend, aux LDE, aux tree, the aux root into the sponge and the 604 quotient weights
-// (tvm_front_quotient_weights), the quotient and the segments -- with challenges and weights read where the device left them.  The
-// download of the block's head and replay_front are owed afterwards.  false: the call does not apply (no whole trees on one GPU: the
-// sharded and coset-wise provers; `extend` without `extend_device`; TVMH_OPTION_CHECK_TRACE, which needs the challenges on the host
-// and decides the AIR's mode there) and nothing was queued or enqueued.
-bool ProofSteps::device_front(u64 zeta, u64 poly_len, DeviceBuffer& front, tvm_table*& segments, DeviceBuffer& polys) {
-    if (!whole_trees_here() || (extend && !extend_device) || tvmh_get_option(TVMH_OPTION_CHECK_TRACE)) return false;
-    front = DeviceBuffer(c, TVM_FRONT_BLOCK_WORDS);
-    u64* d = front.ptr();
-    mark("main LDE");
-    extend_master_table(MAIN);
-    mark("main Merkle");
-    const u64* main_tree = commit_whole_tree(MAIN);
-    if (!main_tree) throw Error(TVM_ERR_DEVICE, "device_front: no whole main tree");
-    c.check(tvm_front_challenges(c.raw(), main_tree, ps.sponge_state(), claim.program_digest, claim.input.data(), claim.input.size(),
-                                 claim.output.data(), claim.output.size(), d), "tvm_front_challenges");
-    mark("extend");
-    if (extend_device) extend_device(d + TVM_FRONT_CHALLENGES);
-    mark("aux LDE");
-    extend_master_table(AUX);
-    mark("aux Merkle");
-    const u64* aux_tree = commit_whole_tree(AUX);
-    if (!aux_tree) throw Error(TVM_ERR_DEVICE, "device_front: no whole aux tree");
-    c.check(tvm_front_quotient_weights(c.raw(), aux_tree, d), "tvm_front_quotient_weights");
-    mark("AIR quotients");
-    segments = quotient_segments(d + TVM_FRONT_CHALLENGES, d + TVM_FRONT_WEIGHTS, zeta, polys, poly_len);
-    return true;
-}
-void ProofSteps::fetch_front(const u64* d_front, std::vector<u64>& head, bool wait) {
-    head.resize(TVM_FRONT_HEAD_WORDS);
-    c.check(tvm_front_block(c.raw(), d_front, head.data(), head.size(), wait ? 1 : 0), "tvm_front_block");
-}
-// The host's side of device_front, once the head of the block is here: the two roots are enqueued from it and both samplings replayed
-// on this host's sponge, which must arrive at the same 63 challenges, the same weight scalar and the same state.
-void ProofSteps::replay_front(const std::vector<u64>& head) {
-    const u64* b = head.data();
-    auto agree = [](bool same, const char* what) {
-        if (!same) throw Error(TVM_ERR_DEVICE, std::string("the device's Fiat-Shamir sponge and the host's disagree on ") + what);
-    };
-    ps.enqueue("main root", b + TVM_FRONT_MAIN_ROOT, 5);
-    const std::vector<Xfe> challenges = derive_challenges(ps.sample_scalars(NUM_SAMPLED_CHALLENGES), claim);
-    agree(std::memcmp(challenges[0].c, b + TVM_FRONT_CHALLENGES, 3 * TVM_NUM_CHALLENGES * sizeof(u64)) == 0, "the challenges");
-    ps.enqueue("aux root", b + TVM_FRONT_AUX_ROOT, 5);
-    const Xfe w = ps.sample_scalars(1)[0];
-    agree(std::memcmp(w.c, b + TVM_FRONT_WEIGHT_SCALAR, 3 * sizeof(u64)) == 0, "the scalar of the quotient weights");
-    agree(std::memcmp(ps.sponge_state(), b + TVM_FRONT_STATE, 16 * sizeof(u64)) == 0, "the state after the quotient weights");
-    g_device_front_proofs++;
 }
 
 ProofStream ProofSteps::prove() {
@@ -909,7 +761,8 @@ namespace {
 // The whole tables on one GPU: cached extensions, whole trees, the quotient in coefficient form where the AIR yields it.
 struct WholeSteps : ProofSteps {
     using ProofSteps::ProofSteps;
-    DeviceBuffer nodes[3];   // the three Merkle trees, by Which
+    WholeTables tables;
+    WholeTables* whole() override { return &tables; }
     // TVMH_OPTION_TRACE: the stages of the hot path on stderr beside Stopwatch's laps (1: the stream drained at every boundary)
     const uint64_t trace = tvmh_get_option(TVMH_OPTION_TRACE);
     std::chrono::steady_clock::time_point stage_start;
@@ -924,30 +777,9 @@ struct WholeSteps : ProofSteps {
     ~WholeSteps() { mark(""); }   // (the last stage ends with the proof)
 
     void extend_master_table(Which w) override { master(w).maybe_low_degree_extend_all_columns(); }
-    const tvm_table* segment_table = nullptr;   // as commit(QUOT, ..) saw it
-    bool whole_tables_and_trees(const tvm_table* tables[3], const u64* trees[3]) override {
-        if (!segment_table || !nodes[MAIN].ptr() || !nodes[AUX].ptr() || !nodes[QUOT].ptr()) return false;
-        tables[MAIN] = main.table(), tables[AUX] = aux.table(), tables[QUOT] = segment_table;
-        for (int w = 0; w < 3; w++) trees[w] = nodes[w].ptr();
-        return true;
-    }
     Words commit(Which w, const tvm_table* segments) override {
-        build_tree(w, segments);
-        return merkle_root(c, nodes[w]);
-    }
-    const u64* commit_whole_quotient_tree(const tvm_table* segments) override {   // (the root stays on the device: no round trip)
-        build_tree(QUOT, segments);
-        return nodes[QUOT].ptr();
-    }
-    bool whole_trees_here() const override { return true; }
-    const u64* commit_whole_tree(Which w) override {
-        build_tree(w, nullptr);
-        return nodes[w].ptr();
-    }
-    void build_tree(Which w, const tvm_table* segments) {
-        if (w == QUOT) segment_table = segments;
-        nodes[w] = DeviceBuffer(c, 10 * p.ldt.length);
-        c.check(tvm_table_merkle_tree(c.raw(), w == QUOT ? segments : master(w).table(), p.ldt.length, nodes[w].ptr()), "tvm_table_merkle_tree");
+        build_whole_tree(w, segments);
+        return merkle_root(c, tables.nodes[w]);
     }
     // Where the AIR arrives at the quotient's coefficients (valid-trace mode on a long trace) the segments are taken from them, and
     // only elsewhere (exact mode, short traces, other expansion factors) a codeword is made and interpolated.
@@ -998,7 +830,7 @@ struct WholeSteps : ProofSteps {
     Openings open(const tvm_table* segments, const std::vector<u64>& indices) override {
         const std::vector<u64> auth_idx = auth_node_indices(p.ldt.length, indices);
         GatherBatch batch;
-        for (const DeviceBuffer& tree : nodes) batch.add(tree.ptr(), 5, auth_idx);
+        for (const DeviceBuffer& tree : whole()->nodes) batch.add(tree.ptr(), 5, auth_idx);
         batch.run(c);
         Openings o;
         o.rows[MAIN] = main.reveal_rows(indices);
@@ -1020,7 +852,7 @@ ProofStream Prover::prove() {
 // ------------------------------------------------------------------------------------------------ STIR
 namespace {
 const double LOG2_FIELD_SIZE_F = 191.99999999899228;  // ReedSolomonCode::LOG2_FIELD_SIZE (low_degree_test/mod.rs:226)
-const int LOG2_FIELD_SIZE = 64 * 3, LOG2_DOMAIN_SHRINKAGE = 1, LOG2_FOLDING_FACTOR = 2;  // stir.rs:404-412
+const int LOG2_FIELD_SIZE = 64 * 3, LOG2_FOLDING_FACTOR = 2;  // stir.rs:404-412 (LOG2_DOMAIN_SHRINKAGE: host_internal.hpp)
 // ReedSolomonCode with proven soundness (mod.rs:93-170)
 double proximity_parameter(unsigned log2_expansion) {
     const double margin = std::sqrt(1.0 / (double)(1ull << log2_expansion));
@@ -1100,89 +932,6 @@ Stir Stir::for_stark(u64 padded_height, unsigned security_level, unsigned log2_e
         if (stir.initial_domain.length >= randomized_trace_len_for(padded_height, stir.num_trace_randomizers()) << log2_expansion) return stir;
     }
     throw Error(TVM_ERR_INVALID_ARGUMENT, "no suitable STIR parameters found");
-}
-
-namespace {
-std::vector<u64> unique_folded(const std::vector<u64>& indices, u64 folded_len) {  // .map(|i| i % len).unique()
-    std::vector<u64> out;
-    for (u64 i : indices) {
-        const u64 f = i % folded_len;
-        if (std::find(out.begin(), out.end(), f) == out.end()) out.push_back(f);
-    }
-    return out;
-}
-}  // namespace
-
-static std::atomic<uint64_t> g_device_stir_proofs{0};   // tvmh_device_stir_proofs
-// TVMH_OPTION_DEVICE_STIR: the whole of Stir::prove in one call, the sponge on the device (tvm_stir_prove_rounds: two stream
-// synchronisations, no host work between the rounds) -- then every enqueue and every sampling is replayed on this host's sponge, which
-// must arrive at the same scalars, the same indices and the same state.  false: the call does not apply (a round with more than
-// TVM_TAIL_MAX_INDICES in-domain queries, or a full round with more than 256 queries in all) and nothing was enqueued.
-bool Stir::prove_on_device(const Context& c, const u64* d_codeword, ProofStream& ps, std::vector<u64>& first_round_indices) const {
-    const uint32_t R = (uint32_t)round_queries.size();
-    std::vector<u64> pairs, queries;
-    u64 n_ood_all = 0, n_queries_all = final_num_in_domain_queries, n_final = initial_domain.length;
-    for (const auto& q : round_queries) {
-        pairs.push_back(q.first), pairs.push_back(q.second), queries.push_back(q.first);
-        n_ood_all += q.second, n_queries_all += q.first;
-    }
-    queries.push_back(final_num_in_domain_queries);
-    for (uint32_t r = 0; r <= R; r++) n_final = (n_final + folding_factor - 1) / folding_factor;
-    const u64 capacity = tvm_stir_prove_rounds_payload_bound(initial_domain.c(), (uint32_t)folding_factor, R, pairs.data(), final_num_in_domain_queries);
-    u64 state[16], n_payload = 0;
-    std::vector<u64> roots(5 * ((size_t)R + 1)), indices(n_queries_all), unique(n_queries_all), unique_counts((size_t)R + 1), final_words(3 * n_final),
-        directory(4 * ((size_t)R + 1)), ood_values(3 * n_ood_all + 1);
-    std::vector<Xfe> scalars(2 * (size_t)R + 1 + n_ood_all);
-    // (room for the bound -- every index distinct, full paths -- but not filled: only the pages the proof's words reach are touched)
-    const std::unique_ptr<u64[]> payload(new u64[capacity ? capacity : 1]);
-    const int32_t status = tvm_stir_prove_rounds(c.raw(), ps.sponge_state(), d_codeword, initial_domain.c(), (uint32_t)folding_factor, R, pairs.data(),
-                                                 final_num_in_domain_queries, final_degree, state, roots.data(), scalars[0].c, ood_values.data(),
-                                                 indices.data(), unique.data(), unique_counts.data(), final_words.data(), directory.data(),
-                                                 payload.get(), capacity, &n_payload);
-    if (status == TVM_NOT_APPLICABLE) return false;
-    c.check(status, "tvm_stir_prove_rounds");
-    auto agree = [](bool same, const char* what) {
-        if (!same) throw Error(TVM_ERR_DEVICE, std::string("the device's Fiat-Shamir sponge and the host's disagree on ") + what);
-    };
-    auto same_scalars = [&](const std::vector<Xfe>& mine, const Xfe* theirs) {
-        return mine.empty() || std::memcmp(mine[0].c, theirs->c, mine.size() * sizeof(Xfe)) == 0;
-    };
-    // tree t's response: the indices the host samples must be the device's, and their first occurrences mod the folded length its list
-    const Xfe* scalar = scalars.data();
-    const u64 *raw = indices.data(), *list = unique.data();
-    ArithmeticDomain domain = initial_domain;
-    auto respond = [&](uint32_t t) {
-        const std::vector<u64> queried = ps.sample_indices(domain.length, queries[t]);
-        agree(std::equal(queried.begin(), queried.end(), raw), "the STIR query indices");
-        const std::vector<u64> folded = unique_folded(queried, domain.length / folding_factor);
-        agree(folded.size() == unique_counts[t] && std::equal(folded.begin(), folded.end(), list), "the STIR query indices without repeats");
-        ps.enqueue("stir response leafs", payload.get() + directory[4 * t], directory[4 * t + 1], folding_factor * 3);
-        ps.enqueue("stir response auth", payload.get() + directory[4 * t + 2], directory[4 * t + 3]);
-        raw += queries[t], list += queries[t];
-        return queried;
-    };
-    ps.enqueue("stir root", roots.data(), 5);
-    const u64* values = ood_values.data();
-    for (uint32_t r = 0; r < R; r++) {
-        const u64 n_ood = round_queries[r].second;
-        agree(same_scalars(ps.sample_scalars(1), scalar), "a STIR folding randomness");
-        ps.enqueue("stir root", roots.data() + 5 * ((size_t)r + 1), 5);
-        agree(same_scalars(ps.sample_scalars(n_ood), scalar + 1), "the STIR out-of-domain points");
-        ps.enqueue("stir ood values", n_ood ? values : nullptr, 3 * n_ood);
-        const std::vector<u64> queried = respond(r);
-        if (r == 0) first_round_indices = queried;
-        agree(same_scalars(ps.sample_scalars(1), scalar + 1 + n_ood), "a STIR degree-correction randomness");
-        scalar += 2 + n_ood, values += 3 * n_ood;
-        ArithmeticDomain next = domain.pow(1ull << LOG2_DOMAIN_SHRINKAGE);
-        domain = next.with_offset(mont_mul(next.offset, domain.offset));
-    }
-    agree(same_scalars(ps.sample_scalars(1), scalar), "the final STIR folding randomness");
-    ps.enqueue("stir final polynomial", final_words.data(), final_words.size());
-    const std::vector<u64> queried = respond(R);
-    if (R == 0) first_round_indices = queried;
-    agree(std::memcmp(state, ps.sponge_state(), sizeof(state)) == 0, "the state after STIR");
-    g_device_stir_proofs++;
-    return true;
 }
 
 // Stir::prove (stir.rs:885-993).  Device work through the C ABI: stacked Merkle trees, polynomial folding, the witness
@@ -1454,11 +1203,6 @@ extern "C" void tvmh_set_option(uint32_t option, uint64_t value) {
     if (option >= 1 && option <= 9) g_options[option].store(value);
 }
 extern "C" uint64_t tvmh_get_option(uint32_t option) { return option >= 1 && option <= 9 ? g_options[option].load() : 0; }
-
-extern "C" uint64_t tvmh_device_tail_proofs(void) { return triton_vm::g_device_tail_proofs.load(); }
-extern "C" uint64_t tvmh_device_stir_proofs(void) { return triton_vm::g_device_stir_proofs.load(); }
-extern "C" uint64_t tvmh_device_middle_proofs(void) { return triton_vm::g_device_middle_proofs.load(); }
-extern "C" uint64_t tvmh_device_front_proofs(void) { return triton_vm::g_device_front_proofs.load(); }
 
 extern "C" int32_t tvmh_prove(tvm_ctx* ctx, uint32_t log2_padded_height, uint64_t num_trace_randomizers,
                               uint64_t num_collinearity_checks, uint32_t log2_expansion, const uint64_t* d_main_trace,

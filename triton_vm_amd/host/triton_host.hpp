@@ -529,7 +529,8 @@ extern "C" int32_t tvmh_check_execution(tvm_ctx* ctx, const tvm_aet* aet, uint32
 // same proof, word for word.  Default 0.  STIR proofs, the sharded and coset-wise provers, and a proof with more than
 // TVM_TAIL_MAX_INDICES collinearity checks (TVM_NOT_APPLICABLE) keep the host's path whatever the value.
 #define TVMH_OPTION_DEVICE_TAIL 6
-// how many proofs of this process took that path so far (a proof it does not apply to is not counted: tests and the timing tool ask)
+// how many proofs of this process took that path so far (a proof it does not apply to is not counted: tests and the timing tool ask).
+// The four TVMH_OPTION_DEVICE_* stretches, their replays on the host's sponge and their counters: device_transcript.cpp
 extern "C" uint64_t tvmh_device_tail_proofs(void);
 // TVMH_OPTION_DEVICE_STIR != 0: Stir::prove -- wherever it is called: the single-GPU, the sharded and the coset-wise prover, tvmh_stir_prove --
 // runs all its rounds in one call with the sponge on the device (tvm_stir_prove_rounds: two stream synchronisations instead of about six
