@@ -175,7 +175,12 @@ int32_t tvm_synthetic_fill(tvm_ctx* ctx, uint64_t* d_data, uint64_t n_words, uin
  * chains in csrc/field.h (BFieldElement's Add/Sub/Mul, twenty-first; KAT triton-constraint-builder/src/codegen.rs:926-944)
  * and for the shift forms of csrc/ntt_shift.h.  op 32 + 4K + 2*dit + inverse (K = 1..4): the in-register transforms of
  * 2^K points with power-of-two twiddles on consecutive groups of 2^K words of d_a (d_b unused): dit = bit-reversed in /
- * natural out, else natural in / bit-reversed out; inverse = with the inverse root (no scaling by 2^-K). */
+ * natural out, else natural in / bit-reversed out; inverse = with the inverse root (no scaling by 2^-K).
+ * The words that may leave the canonical range (csrc/ntt_shift.h: canon_plan): op 5 = bfe_add_folded (one operand canonical, the
+ * other any 64-bit word; some 64-bit representative of the sum), op 6 = bfe_canon of d_a; ops 1 and 4 take any 64-bit word as the
+ * minuend / the multiplicand.  op 64 + 2 (4K + 2*dit + inverse) + owed_all (K = 2..4): the lazy form of the transform above, its
+ * outputs owed canonical all (1) or none (0) and the inputs the plan does not need canonical free to be any word;
+ * op 112 + 2i + owed_all (i = 0..2): the same for the 16-point decimation-in-time transform at the points 2^(39 (i + 1)) w^j. */
 int32_t tvm_field_op(tvm_ctx* ctx, int32_t op, const uint64_t* d_a, const uint64_t* d_b, uint64_t* d_out, uint64_t n);
 /* The 16-point transform with power-of-two twiddles (decimation in time: bit-reversed in, natural out, no scaling) on n_groups
  * consecutive groups of 16 words, in the two forms the device has: form bit 0 = with the inverse root, bit 1 = on the matrix cores

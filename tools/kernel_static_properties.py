@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Static properties of the kernels in the built product library: VGPRs, scratch bytes per lane, LDS, code size -- read from the
 code object's metadata notes (llvm-readelf --notes of the gfx950 code object bundled in libtriton_hip.so).
-usage: python tools/kernel_static_properties.py [filter-substring ...]"""
+usage: python tools/kernel_static_properties.py [--lib=PATH] [filter-substring ...]
+(--lib: another build of the library, e.g. an A/B variant triton_vm_amd/libtriton_hip_<variant>.so)"""
 import os
 import re
 import subprocess
@@ -14,6 +15,10 @@ LLVM = "/opt/rocm/lib/llvm/bin"
 
 
 def main(filters):
+    global LIB
+    for f in [f for f in filters if f.startswith("--lib=")]:
+        LIB = os.path.abspath(f[len("--lib="):])
+        filters.remove(f)
     with tempfile.TemporaryDirectory() as tmp:
         # the fat binary sits in the .hip_fatbin section: one offload bundle per translation unit, concatenated
         subprocess.check_call(["objcopy", "-O", "binary", "--only-section=.hip_fatbin", LIB, f"{tmp}/fatbin"])
@@ -37,7 +42,7 @@ def main(filters):
             pass
         rows.append((name.split("(")[0], int(get("vgpr_count").group(1)), int(get("private_segment_fixed_size").group(1)),
                      int(get("group_segment_fixed_size").group(1)), int(get("sgpr_count").group(1))))
-    print("# kernel, VGPRs, scratch B/lane, static LDS B, SGPRs   (from the gfx950 code object of triton_vm_amd/libtriton_hip.so)")
+    print(f"# kernel, VGPRs, scratch B/lane, static LDS B, SGPRs   (from the gfx950 code object of {os.path.relpath(LIB, ROOT)})")
     for r in sorted(rows):
         if not filters or any(f in r[0] for f in filters):
             print(f"  {r[0]:70s} {r[1]:5d} {r[2]:6d} {r[3]:8d} {r[4]:5d}")

@@ -1,11 +1,20 @@
 #!/usr/bin/env python3
 """Summarise a rocprofv3 (rocpd sqlite) kernel trace as a per-kernel table (like --stats).
-Usage: python tools/rocprof_summary.py <results.db> [> profiles/NAME.txt]"""
+Usage: python tools/rocprof_summary.py <results.db> [--by-grid SUBSTRING ...] [> profiles/NAME.txt]
+--by-grid: after the table, the launches of the kernels whose name contains one of the substrings, by (kernel, grid, workgroup)."""
 import sqlite3
 import sys
 
 
-def main(path):
+def by_grid(cur, patterns):
+    print("# launches by (kernel, grid x, grid y, workgroup): calls, total ms, mean / min / max us")
+    for pat in patterns:
+        for r in cur.execute("select name, grid_x, grid_y, workgroup_x, count(*), sum(end-start), avg(end-start), min(end-start), max(end-start) "
+                             "from kernels where name like ? group by name, grid_x, grid_y, workgroup_x order by name, 6 desc", (f"%{pat}%",)):
+            print(f"{r[0][:58]:58s} {r[1]:9d} {r[2]:6d} {r[3]:5d} {r[4]:6d} {r[5] / 1e6:10.3f} {r[6] / 1e3:10.1f} {r[7] / 1e3:10.1f} {r[8] / 1e3:10.1f}")
+
+
+def main(path, patterns=()):
     cur = sqlite3.connect(path).cursor()
     rows = list(cur.execute(
         "select name, count(*), sum(end-start), avg(end-start), min(end-start), max(end-start), "
@@ -18,7 +27,9 @@ def main(path):
     for r in rows:
         print(f"{r[0][:58]:58s} {r[1]:6d} {r[2] / 1e6:10.3f} {r[3] / 1e3:10.1f} {r[4] / 1e3:10.1f} {r[5] / 1e3:10.1f} "
               f"{100 * r[2] / total:6.1f} {r[6]:5d} {r[7]:5d} {r[8]:5d} {r[9]:7d} {r[10]:7d} {r[11]:5d}")
+    if patterns:
+        by_grid(cur, patterns)
 
 
 if __name__ == "__main__":
-    main(sys.argv[1])
+    main(sys.argv[1], [a for a in sys.argv[3:]] if len(sys.argv) > 3 and sys.argv[2] == "--by-grid" else ())

@@ -39,7 +39,7 @@ int32_t tvm_synthetic_fill(tvm_ctx* c, uint64_t* d, uint64_t n, uint64_t seed) {
 }  // extern "C"
 namespace tvm {
 // out[i] = a[i] op b[i] through the device arithmetic of field.h (op: 0 add, 1 sub, 2 mul, 3 a^7, 4: a * 2^b for a plain
-// exponent b < 192 through the shift forms of ntt_shift.h)
+// exponent b < 192 through the shift forms of ntt_shift.h, 5: bfe_add_folded, 6: bfe_canon of a)
 template <int S>
 TVM_D u64 mul_pow2_dispatch(u64 x, int s) {
     if constexpr (S < 0) return 0;
@@ -54,6 +54,8 @@ __global__ void k_field_op(int op, const u64* __restrict__ a, const u64* __restr
     else if (op == 1) r = bfe_sub(x, y);
     else if (op == 2) r = bfe_mul(x, y);
     else if (op == 3) r = bfe_mul(bfe_mul(bfe_sqr(bfe_sqr(x)), bfe_sqr(x)), x);
+    else if (op == 5) r = bfe_add_folded(x, y);
+    else if (op == 6) r = bfe_canon(x);
     else {
         const int s = (int)(y % 192);
         r = mul_pow2_dispatch<95>(x, s % 96);
@@ -81,12 +83,59 @@ static void launch_pow2_points(tvm_ctx* c, int dit, int inverse, const u64* a, u
     else if (inverse) TVM_LAUNCH((k_pow2_points<K, false, true>), grid, block, 0, c->stream, a, out, n_groups);
     else TVM_LAUNCH((k_pow2_points<K, false, false>), grid, block, 0, c->stream, a, out, n_groups);
 }
+// the lazy forms (ntt_shift.h: canon_plan): outputs owed canonical all or none, the inputs declared canonical exactly those the
+// plan needs -- a caller may hand any 64-bit word at the others.  op = 64 + 2 (4 K + 2 dit + inverse) + owed_all, K = 2 .. 4;
+// op = 112 + 2 i + owed_all: the 16-point decimation-in-time transform at the points 2^(39 (i + 1)) w^j
+template <int K, bool DIT, bool INVERSE, int SHIFT, bool OWED_ALL>
+__global__ void k_pow2_points_lazy(const u64* __restrict__ a, u64* __restrict__ out, u64 n_groups) {
+    const u64 g = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= n_groups) return;
+    constexpr int OWED = OWED_ALL ? (1 << (1 << K)) - 1 : 0;
+    constexpr unsigned IN = canon_plan(K, DIT, INVERSE, SHIFT, ~0u, (unsigned)OWED).need_in;
+    u64 x[1 << K];
+#pragma unroll
+    for (int e = 0; e < (1 << K); e++) x[e] = a[(g << K) + e];
+    if constexpr (SHIFT == 0) ntt_pow2_points<K, DIT, INVERSE, OWED, IN>(x);
+    else ntt_pow2_points_shifted<K, SHIFT, OWED, IN>(x);
+#pragma unroll
+    for (int e = 0; e < (1 << K); e++) out[(g << K) + e] = x[e];
+}
+template <int K, int SHIFT = 0>
+static void launch_pow2_points_lazy(tvm_ctx* c, int dit, int inverse, int owed_all, const u64* a, u64* out, u64 n_groups) {
+    const dim3 grid((unsigned)((n_groups + 63) / 64)), block(64);
+#define TVM_LAZY_FORM(D, I)                                                                                                  \
+    do {                                                                                                                     \
+        if (owed_all) TVM_LAUNCH((k_pow2_points_lazy<K, D, I, SHIFT, true>), grid, block, 0, c->stream, a, out, n_groups);  \
+        else TVM_LAUNCH((k_pow2_points_lazy<K, D, I, SHIFT, false>), grid, block, 0, c->stream, a, out, n_groups);          \
+    } while (0)
+    if constexpr (SHIFT != 0) TVM_LAZY_FORM(true, false);
+    else if (dit && inverse) TVM_LAZY_FORM(true, true);
+    else if (dit) TVM_LAZY_FORM(true, false);
+    else if (inverse) TVM_LAZY_FORM(false, true);
+    else TVM_LAZY_FORM(false, false);
+#undef TVM_LAZY_FORM
+}
 }  // namespace tvm
 extern "C" {
 int32_t tvm_field_op(tvm_ctx* c, int32_t op, const uint64_t* d_a, const uint64_t* d_b, uint64_t* d_out, uint64_t n) {
     const bool points = op >= 32 && op < 32 + 5 * 4;  // 32 + 4 K + 2 dit + inverse: transforms of 2^K points, K = 1 .. 4
-    if (!c || op < 0 || (op > 4 && !points) || (n && (!d_a || !d_b || !d_out))) return set_error(c, TVM_ERR_INVALID_ARGUMENT, "tvm_field_op arguments");
+    const bool lazy = op >= 64 + 2 * 4 * 2 && op < 64 + 2 * 4 * 5, lazy_shifted = op >= 112 && op < 118;   // (k_pow2_points_lazy)
+    if (!c || op < 0 || (op > 6 && !points && !lazy && !lazy_shifted) || (n && (!d_a || !d_b || !d_out))) return set_error(c, TVM_ERR_INVALID_ARGUMENT, "tvm_field_op arguments");
     if (!n) return TVM_OK;
+    if (lazy || lazy_shifted) {
+        const int form = (op - 64) >> 1, owed_all = op & 1, K = lazy ? form >> 2 : 4;
+        if (n % (1ull << K)) return set_error(c, TVM_ERR_INVALID_ARGUMENT, "tvm_field_op: whole groups of 2^K words");
+        if (lazy_shifted) {
+            const int i = (op - 112) >> 1;
+            if (i == 0) tvm::launch_pow2_points_lazy<4, 39>(c, 1, 0, owed_all, d_a, d_out, n >> 4);
+            else if (i == 1) tvm::launch_pow2_points_lazy<4, 78>(c, 1, 0, owed_all, d_a, d_out, n >> 4);
+            else tvm::launch_pow2_points_lazy<4, 117>(c, 1, 0, owed_all, d_a, d_out, n >> 4);
+        } else if (K == 2) tvm::launch_pow2_points_lazy<2>(c, (form >> 1) & 1, form & 1, owed_all, d_a, d_out, n >> 2);
+        else if (K == 3) tvm::launch_pow2_points_lazy<3>(c, (form >> 1) & 1, form & 1, owed_all, d_a, d_out, n >> 3);
+        else tvm::launch_pow2_points_lazy<4>(c, (form >> 1) & 1, form & 1, owed_all, d_a, d_out, n >> 4);
+        TVM_HIP_CHECK(c, hipGetLastError());
+        return TVM_OK;
+    }
     if (points) {
         const int K = (op - 32) >> 2, dit = (op >> 1) & 1, inverse = op & 1;
         if (K < 1 || K > 4 || n % (1ull << K)) return set_error(c, TVM_ERR_INVALID_ARGUMENT, "tvm_field_op: whole groups of 2^K words");

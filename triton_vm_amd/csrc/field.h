@@ -54,6 +54,46 @@ TVM_HD u64 bfe_add(u64 a, u64 b) {
     return (s < a || s >= TVM_P) ? s + TVM_EPS : s;
 #endif
 }
+// a + b for ANY 64-bit word a and a canonical b (or the other way round): some 64-bit representative of the residue, not
+// necessarily below p.  s = a + b mod 2^64; after a carry s = a + b - 2^64 < p = 2^64 - EPS, so adding EPS (= 2^64 mod p)
+// cannot wrap a second time -- the tail TIP5_F2..F4 of tip5.h.  5 VALU instructions and three pairs of wait states where
+// bfe_add has 6, a scalar one and four.
+TVM_HD u64 bfe_add_folded(u64 a, u64 b) {
+#ifdef TVM_FIELD_ASM
+    u32 s0, s1, m;
+    asm("v_add_co_u32 %[s0], vcc, %[a0], %[b0]\n\t" TVM_VCC_WAIT
+        "v_addc_co_u32 %[s1], vcc, %[a1], %[b1], vcc\n\t" TVM_VCC_WAIT
+        "v_cndmask_b32_e64 %[m], 0, -1, vcc\n\t"
+        "v_add_co_u32 %[s0], vcc, %[s0], %[m]\n\t" TVM_VCC_WAIT
+        "v_addc_co_u32 %[s1], vcc, 0, %[s1], vcc"
+        : [s0] "=&v"(s0), [s1] "=&v"(s1), [m] "=&v"(m)
+        : [a0] "v"((u32)a), [a1] "v"((u32)(a >> 32)), [b0] "v"((u32)b), [b1] "v"((u32)(b >> 32))
+        : "vcc");
+    return ((u64)s1 << 32) | s0;
+#else
+    u64 s = a + b;
+    return (s < a) ? s + TVM_EPS : s;
+#endif
+}
+// the canonical word of any 64-bit representative: x - p where x >= p (x + EPS carries exactly then).  4 VALU instructions.
+TVM_HD u64 bfe_canon(u64 x) {
+#ifdef TVM_FIELD_ASM
+    u32 t0, t1, r0, r1;
+    asm("v_add_co_u32 %[t0], vcc, -1, %[x0]\n\t" TVM_VCC_WAIT
+        "v_addc_co_u32 %[t1], vcc, 0, %[x1], vcc\n\t" TVM_VCC_WAIT
+        "v_cndmask_b32 %[r0], %[x0], %[t0], vcc\n\t"
+        "v_cndmask_b32 %[r1], %[x1], %[t1], vcc"
+        : [t0] "=&v"(t0), [t1] "=&v"(t1), [r0] "=&v"(r0), [r1] "=&v"(r1)
+        : [x0] "v"((u32)x), [x1] "v"((u32)(x >> 32))
+        : "vcc");
+    return ((u64)r1 << 32) | r0;
+#else
+    return x >= TVM_P ? x - TVM_P : x;
+#endif
+}
+// a - b.  The subtrahend b must be canonical.  The minuend a may be ANY 64-bit word: after a borrow the difference is
+// a - b + 2^64 >= 2^64 - b > EPS, so taking EPS off cannot borrow again and the result is a representative of a - b; it is the
+// canonical word whenever a is canonical (no borrow: a - b <= a < p; borrow: a - b + p < p).
 TVM_HD u64 bfe_sub(u64 a, u64 b) {
 #ifdef TVM_FIELD_ASM
     // d = a - b; a borrow means d is short by p = 2^64 - EPS, i.e. subtract EPS once more

@@ -198,7 +198,15 @@ struct RowSync {
         else tvm_lds_barrier();
     }
 };
-template <bool DIT, int K, int L, int LOGN, int ROOT, int TWB = TVM_TW_BATCH, int LPR = 64, class Sync = RowSync<LPR>>
+// LZ, lazy sums (ntt_shift.h: canon_plan): 0 = every word of the row stays canonical; 1 / 2 = between the groups of a transform the
+// words are any 64-bit representatives wherever the next reader allows it, and the transform's LAST group leaves canonical words
+// (1: they are stored, or added to) or any representatives (2: the caller multiplies every one of them by a table value).
+//   * The twiddle step makes elements 1 .. 2^K - 1 canonical (bfe_mul by a canonical table value), so only element 0 of a group
+//     is open.  Decimation in time: it is the group's own x[0], a position the plan knows -- an input declared free, canonicalised
+//     first in a last group that owes canonical words.  Decimation in frequency: the next group reads it at a position that depends
+//     on the lane, so it is canonicalised after the butterflies (4 instructions; a 16-point group folds 15 sums, each a vector and a scalar one less).
+//   * The first group's inputs are canonical: the callers load them from memory.
+template <bool DIT, int K, int L, int LOGN, int ROOT, int TWB = TVM_TW_BATCH, int LPR = 64, int LZ = 0, class Sync = RowSync<LPR>>
 TVM_D void row_ntt_group(u64* row, const u64* __restrict__ tw, int lane, Sync& sync) {
     static_assert(ROOT == 1 || ROOT == 2, "the domains' own roots of unity only");
     constexpr int R = 1 << K, NG = 1 << (LOGN - K);
@@ -225,7 +233,17 @@ TVM_D void row_ntt_group(u64* row, const u64* __restrict__ tw, int lane, Sync& s
                 }
             }
         }
-        ntt_pow2_points<K, DIT, ROOT == 2>(x);
+        constexpr bool LAST = DIT ? (L + K == LOGN) : (L == 0), OWE = LAST && LZ == 1;
+        constexpr unsigned ALL = (1u << R) - 1;
+        if constexpr (LZ == 0) {
+            ntt_pow2_points<K, DIT, ROOT == 2>(x);
+        } else if constexpr (DIT) {
+            if constexpr (OWE && L > 0) x[0] = bfe_canon(x[0]);
+            ntt_pow2_points<K, true, ROOT == 2, OWE ? (int)ALL : 0, (L > 0 && !OWE) ? (ALL & ~1u) : ALL>(x);
+        } else {
+            ntt_pow2_points<K, false, ROOT == 2, OWE ? (int)ALL : 0, ALL>(x);
+            if constexpr (!LAST) x[0] = bfe_canon(x[0]);
+        }
         if constexpr (L > 0 && !DIT) {
 #pragma unroll
             for (int e = 1; e < R; e++) {
@@ -240,27 +258,32 @@ TVM_D void row_ntt_group(u64* row, const u64* __restrict__ tw, int lane, Sync& s
     }
     sync();
 }
-template <bool DIT, int K, int L, int LOGN, int ROOT, int TWB = TVM_TW_BATCH, int LPR = 64>
+template <bool DIT, int K, int L, int LOGN, int ROOT, int TWB = TVM_TW_BATCH, int LPR = 64, int LZ = 0>
 TVM_D void row_ntt_group(u64* row, const u64* __restrict__ tw, int lane) {
     RowSync<LPR> sync;
-    row_ntt_group<DIT, K, L, LOGN, ROOT, TWB, LPR, RowSync<LPR>>(row, tw, lane, sync);
+    row_ntt_group<DIT, K, L, LOGN, ROOT, TWB, LPR, LZ, RowSync<LPR>>(row, tw, lane, sync);
 }
 // (`sync`: called after every group; the default is the wavefront-level wait for rows of <= 64 lanes and the workgroup barrier for
 // rows of 128 -- the kernels with two wavefronts per row pass their pair synchronisation instead)
-template <bool DIT, int MAXK, int LOGN, int ROOT, int DONE = 0, int LPR = 64, class Sync = RowSync<LPR>>
+template <bool DIT, int MAXK, int LOGN, int ROOT, int DONE = 0, int LPR = 64, int LZ = 0, class Sync = RowSync<LPR>>
 TVM_D void row_ntt(u64* row, const u64* __restrict__ tw, int lane, Sync& sync) {
     if constexpr (DONE < LOGN) {
         constexpr int k = (LOGN - DONE) >= MAXK ? MAXK : (LOGN - DONE);
         constexpr int l = DIT ? DONE : (LOGN - DONE - k);
-        row_ntt_group<DIT, k, l, LOGN, ROOT, TVM_TW_BATCH, LPR, Sync>(row, tw, lane, sync);
-        row_ntt<DIT, MAXK, LOGN, ROOT, DONE + k, LPR, Sync>(row, tw, lane, sync);
+        row_ntt_group<DIT, k, l, LOGN, ROOT, TVM_TW_BATCH, LPR, LZ, Sync>(row, tw, lane, sync);
+        row_ntt<DIT, MAXK, LOGN, ROOT, DONE + k, LPR, LZ, Sync>(row, tw, lane, sync);
     }
 }
-template <bool DIT, int MAXK, int LOGN, int ROOT, int DONE = 0, int LPR = 64>
+template <bool DIT, int MAXK, int LOGN, int ROOT, int DONE = 0, int LPR = 64, int LZ = 0>
 TVM_D void row_ntt(u64* row, const u64* __restrict__ tw, int lane) {
     RowSync<LPR> sync;
-    row_ntt<DIT, MAXK, LOGN, ROOT, DONE, LPR, RowSync<LPR>>(row, tw, lane, sync);
+    row_ntt<DIT, MAXK, LOGN, ROOT, DONE, LPR, LZ, RowSync<LPR>>(row, tw, lane, sync);
 }
+// the row kernels of 256 .. 1024 points take the lazy sums (TVM_LDE_LAZY_SUMS, ntt_shift.h); the 2048-point ones do not
+template <int LOGN>
+struct LdeLazy {
+    static constexpr bool on = TVM_LDE_LAZY_SUMS && LOGN <= 10;
+};
 
 // ------------------------------------------------------------------------------------------------
 // Generic two-pass transform of `ncols` columns (grid.y), natural order in and out.
@@ -737,7 +760,7 @@ __global__ void __launch_bounds__(64 * WAVES, LOGN <= 10 ? 4 : 2) k_lde_pass3_ro
 #pragma unroll
             for (int e = 0; e < E; e++) nxt[e] = TVM_LOAD_STREAM(&zc[((k * n2 + j1) << LOGN) + 64 * e]);
         }
-        row_ntt<true, MAXK, LOGN, 1>(row, tw_lds, lane);
+        row_ntt<true, MAXK, LOGN, 1, 0, 64, LdeLazy<LOGN>::on ? 1 : 0>(row, tw_lds, lane);   // (Z is canonical; so is the table)
         const u64 j1 = rho >> log_x, k = rho & (X - 1);
         const u64 blk = (k * a.pitch + (j1 << LOGN)) >> TVM_RB_LOG;   // the row's first 16-row block of the table
 #pragma unroll 4
@@ -942,7 +965,8 @@ __global__ void __launch_bounds__((1 << (LOGN - 4)) * ROWS, 4) k_lde_pass1_rows(
 #pragma unroll
                 for (int it = 0; it < 16; it++) nxt[it] = TVM_LOAD_STREAM(&in[(u64)it * in_step]);
             }
-            row_ntt<false, 4, LOGN, 2, 0, LPR>(s + (tid / LPR) * ROWW, tw_lds, tid % LPR);
+            // (lazy sums: the last group's words are any representatives -- the store multiplies every one of them by t)
+            row_ntt<false, 4, LOGN, 2, 0, LPR, LdeLazy<LOGN>::on ? 2 : 0>(s + (tid / LPR) * ROWW, tw_lds, tid % LPR);
             tvm_lds_barrier();   // the rows are transformed
             // position p = q0 + LPR * brev4(c) holds index k1 = brev(p) = brev(q0) * 16 + c
             const LdePass1Item item = lde_pass1_item(index, log_tiles);
@@ -1080,7 +1104,11 @@ __global__ void __launch_bounds__(8 << (LOGN - 4), LOGN >= 10 ? 4 : 3) k_lde_pas
     if constexpr (WPR <= 1) tvm_wave_sync();
     else tvm_lds_barrier();   // (the row is loaded, the pair flags are zero)
     // inverse rows step: position q of the row then holds N * t[m1*n1 + m2], m1 = brev(q), m2 = brev(p)
-    if (a.mode != TVM_LDE_FORWARD_ONLY) row_ntt<false, 4, LOGN, 2, 0, LPR>(row, a.tw_a2, rl, row_sync);
+    // (lazy sums: canonical words out -- they are the coefficient form TVM_LDE_INVERSE_ONLY stores, the first group's inputs in the
+    // scale-absorbed form and an operand of the randomizer term's bfe_add)
+    constexpr int LZO = LdeLazy<LOGN>::on ? 0 : -1;   // the owed-output mask of the coset loop's groups: none, or not lazy at all
+    constexpr unsigned ALL16 = 0xFFFFu;
+    if (a.mode != TVM_LDE_FORWARD_ONLY) row_ntt<false, 4, LOGN, 2, 0, LPR, LdeLazy<LOGN>::on ? 1 : 0>(row, a.tw_a2, rl, row_sync);
     if (a.mode == TVM_LDE_INVERSE_ONLY) {
         u64* yw = const_cast<u64*>(a.y) + (u64)vl * n + p * n2 + rl;
         const u64* const rowl = row + TVM_ROW_SKEW(rl);
@@ -1128,10 +1156,12 @@ __global__ void __launch_bounds__(8 << (LOGN - 4), LOGN >= 10 ? 4 : 3) k_lde_pas
             for (int e = 0; e < 16; e++) x[e] = bfe_mul(coef[e], gh[e]);
         }
         if (has_rnd && ln == 0) x[0] = bfe_add(coef[0], bfe_mul(a.zk[k], *r0));   // gamma_k^0 = 1 at position 0
-        if (!ABS || shift == 0) ntt_pow2_points<4, true, false>(x);
-        else if (shift == 1) ntt_pow2_points_shifted<4, 39>(x);
-        else if (shift == 2) ntt_pow2_points_shifted<4, 78>(x);
-        else ntt_pow2_points_shifted<4, 117>(x);
+        // (lazy sums: x[] is canonical -- products, canonical coefficients, the randomizer term's bfe_add; the middle group multiplies
+        // all of this group's outputs but those at its x2[0] in the table form, which it declares free)
+        if (!ABS || shift == 0) ntt_pow2_points<4, true, false, LZO>(x);
+        else if (shift == 1) ntt_pow2_points_shifted<4, 39, LZO>(x);
+        else if (shift == 2) ntt_pow2_points_shifted<4, 78, LZO>(x);
+        else ntt_pow2_points_shifted<4, 117, LZO>(x);
         {
             u64* const out = row + 17 * ln;
 #pragma unroll
@@ -1163,7 +1193,7 @@ __global__ void __launch_bounds__(8 << (LOGN - 4), LOGN >= 10 ? 4 : 3) k_lde_pas
                     if (e % TVM_P2F_TWB == 0) asm volatile("" ::: "memory");
                 }
             }
-            ntt_pow2_points<4, true, false>(x2);
+            ntt_pow2_points<4, true, false, LZO, ABS ? ALL16 : (ALL16 & ~1u)>(x2);   // (the last group multiplies all its inputs)
 #pragma unroll
             for (int e = 0; e < 16; e++) q[17 * e] = x2[e];
         }
@@ -1182,7 +1212,7 @@ __global__ void __launch_bounds__(8 << (LOGN - 4), LOGN >= 10 ? 4 : 3) k_lde_pas
                 const int j = it * R3 + e;   // (a constant after unrolling: the factor's place in the eight 16-byte loads)
                 y8[e] = bfe_mul(q[272 * e], (j & 1) ? f[j >> 1].y : f[j >> 1].x);
             }
-            if constexpr (K3 > 0) ntt_pow2_points<K3, true, false>(y8);
+            if constexpr (K3 > 0) ntt_pow2_points<K3, true, false, LZO>(y8);   // (every output meets u[e] below)
 #pragma unroll
             for (int e = 0; e < R3; e++) q[272 * e] = bfe_mul(y8[e], u[e]);
         }
