@@ -794,6 +794,57 @@ int32_t tvm_verifier_stir_answers(tvm_ctx* ctx, uint32_t folding_factor, uint64_
                                   uint32_t k, const uint64_t* h_quotient_set, const uint64_t* h_answer_polynomial,
                                   const uint64_t* h_degree_correction_randomness, uint64_t* h_out);
 
+/* ---- verifier batch work for MANY proofs per call (csrc/verify_batch.hip) --------------------------------
+ * The stages above that assume one domain, one set of challenges or one set of weights per launch, for n_groups "groups" at
+ * once -- a group is a proof, or one STIR round of a proof.  Host data in, host data out; each call stages through the context's
+ * pool, is ONE launch on the context's stream and synchronises it once, however many groups it is given.  Per-group arguments are
+ * arrays indexed by group ([n_groups]; `const uint64_t* const*`: one host pointer per group; a flat array [n_groups][w]: w words
+ * per group).  h_flags[g]: 0 = group g's results were written; 1 = the group is malformed (what its one-proof entry point answers
+ * TVM_ERR_INVALID_ARGUMENT or TVM_ERR_UNSUPPORTED for) and TVM_NOT_APPLICABLE = the group is beyond the kernel's bound -- nothing
+ * is written for either, and the other groups are not affected.  An error status is for null arguments and device failures.
+ *
+ * tvm_verifier_fri_folds as group g: first_domains[g], n_rounds[g], n_checks[g], h_challenges[g] [n_rounds][3], h_indices[g]
+ * [n_checks], h_a_leaves[g] [n_checks][3], h_b_leaves[g] [n_rounds][n_checks][3] -> h_out[g] [n_checks][3]. */
+int32_t tvm_verifier_fri_folds_batch(tvm_ctx* ctx, uint32_t n_groups, const tvm_domain* first_domains, const uint32_t* n_rounds,
+                                     const uint64_t* n_checks, const uint64_t* const* h_challenges,
+                                     const uint64_t* const* h_indices, const uint64_t* const* h_a_leaves,
+                                     const uint64_t* const* h_b_leaves, uint64_t* const* h_out, uint32_t* h_flags);
+/* The last round of Fri::verify (fri.rs:560-640) up to its comparisons.  Group g: the last codeword h_codewords[g]
+ * [lengths[g]][3] (a power of two) and the point h_points[g][3].  h_roots[g][5]: the root of the codeword's Merkle tree, as
+ * tvm_codeword_merkle_tree builds it; h_values[g][3]: the value at the point of the polynomial of degree < lengths[g] that
+ * interpolates the codeword over ArithmeticDomain::of_length(lengths[g]) (offset one) -- what tvm_interpolate followed by
+ * tvm_evaluate_at_points gives.  One workgroup per group, for codewords of at most TVM_VERIFIER_MAX_LAST_CODEWORD elements: every
+ * last codeword of the parameters derived for security levels 32 to 160 and expansion factors 2 to 8 at 2^8 to 2^24 padded rows
+ * (enumerated: 1024 at most; expansion factors 16 to 256 reach 16384).  A longer one is flagged TVM_NOT_APPLICABLE: take the three
+ * calls named here for it. */
+#define TVM_VERIFIER_MAX_LAST_CODEWORD 1024u
+int32_t tvm_verifier_fri_last_rounds(tvm_ctx* ctx, uint32_t n_groups, const uint64_t* lengths, const uint64_t* const* h_codewords,
+                                     const uint64_t* h_points, uint64_t* h_roots, uint64_t* h_values, uint32_t* h_flags);
+/* tvm_xfe_interpolate as group g: k[g] points h_points[g] [k][3] with values h_values[g] [k][3] -> h_out_coeffs[g] [k][3].
+ * k[g] == 0: nothing to do (flag 0).  k[g] > 256, the limit of the one-workgroup interpolation: TVM_NOT_APPLICABLE (call
+ * tvm_host_xfe_interpolate for that group).  Two points of a group coincide: flag 1, for that group only. */
+int32_t tvm_xfe_interpolate_batch(tvm_ctx* ctx, uint32_t n_groups, const uint32_t* k, const uint64_t* const* h_points,
+                                  const uint64_t* const* h_values, uint64_t* const* h_out_coeffs, uint32_t* h_flags);
+/* tvm_verifier_stir_answers as group g: folding_factors[g], kth_roots[g], h_folding_randomness [n_groups][3], k[g] (0: a first
+ * round; such groups and k > 0 groups may share a call) with h_quotient_sets[g] and h_answer_polynomials[g] [k][3] and
+ * h_degree_correction_randomness [n_groups][3] (read where k[g] > 0), then the n_queries[g] queries: h_values[g] [n][ff][3],
+ * h_coset_roots[g] [n] -> h_out[g] [n][3].  One workgroup per query. */
+int32_t tvm_verifier_stir_answers_batch(tvm_ctx* ctx, uint32_t n_groups, const uint32_t* folding_factors, const uint64_t* kth_roots,
+                                        const uint64_t* h_folding_randomness, const uint32_t* k,
+                                        const uint64_t* const* h_quotient_sets, const uint64_t* const* h_answer_polynomials,
+                                        const uint64_t* h_degree_correction_randomness, const uint64_t* n_queries,
+                                        const uint64_t* const* h_values, const uint64_t* const* h_coset_roots,
+                                        uint64_t* const* h_out, uint32_t* h_flags);
+/* tvm_verifier_deep_values as group g: ldt_domains[g], h_weights_main_aux[g] [470][3], h_weights_quot [n_groups][5][3],
+ * h_weights_deep, h_ood_points and h_ood_values [n_groups][4][3], then the n_rows[g] rows: h_main_rows[g] [n][379], h_aux_rows[g]
+ * [n][91][3], h_quot_rows[g] [n][5][3], h_row_indices[g] [n] -> h_out[g] [n][3].  One workgroup per row. */
+int32_t tvm_verifier_deep_values_batch(tvm_ctx* ctx, uint32_t n_groups, const tvm_domain* ldt_domains,
+                                       const uint64_t* const* h_weights_main_aux, const uint64_t* h_weights_quot,
+                                       const uint64_t* h_weights_deep, const uint64_t* h_ood_points, const uint64_t* h_ood_values,
+                                       const uint64_t* n_rows, const uint64_t* const* h_main_rows,
+                                       const uint64_t* const* h_aux_rows, const uint64_t* const* h_quot_rows,
+                                       const uint64_t* const* h_row_indices, uint64_t* const* h_out, uint32_t* h_flags);
+
 /* host: the 604 AIR constraints on ONE row pair whose main rows are XFieldElements -- what Verifier::verify evaluates on the
  * out-of-domain rows (stark.rs:1466-1491; MasterAuxTable::evaluate_{initial,consistency,transition,terminal}_constraints in
  * this order).  h_main_* [379][3], h_aux_* [91][3], h_challenges [63][3]; h_out [604][3]: initial (81), consistency (97),

@@ -96,10 +96,12 @@ def build_host(backend_lib=None, out=None):
     backend_lib = backend_lib or build()
     out = out or HOST_LIB
     assert os.path.dirname(os.path.abspath(out)) == os.path.dirname(os.path.abspath(backend_lib)), "host library next to its backend"
-    srcs = [os.path.join(HERE, "host", name) for name in ("triton_host.cpp", "device_transcript.cpp", "sharded_host.cpp", "verifier.cpp")]
+    srcs = [os.path.join(HERE, "host", name) for name in ("triton_host.cpp", "device_transcript.cpp", "sharded_host.cpp", "verifier.cpp",
+                                                       "verify_batch.cpp")]
     # (not the backend library's mtime: the host binds to it dynamically through the C ABI, which include/triton_hip.h states --
     # a relinked backend with the same header does not make the host stale)
     deps = srcs + [os.path.join(HERE, "host", "triton_host.hpp"), os.path.join(HERE, "host", "host_internal.hpp"),
+                   os.path.join(HERE, "host", "verifier_internal.hpp"),
                    os.path.join(ROOT, "include", "triton_hip.h")]
     if os.path.exists(out) and all(os.path.getmtime(d) <= os.path.getmtime(out) for d in deps):
         return out

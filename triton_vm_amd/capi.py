@@ -180,6 +180,11 @@ _SIGNATURES = {
                                            C.c_void_p]),
     "tvm_verifier_stir_answers": (C.c_int32, [C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p,
                                               C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "tvm_verifier_fri_folds_batch": (C.c_int32, [C.c_void_p, C.c_uint32] + [C.c_void_p] * 9),
+    "tvm_verifier_fri_last_rounds": (C.c_int32, [C.c_void_p, C.c_uint32] + [C.c_void_p] * 6),
+    "tvm_xfe_interpolate_batch": (C.c_int32, [C.c_void_p, C.c_uint32] + [C.c_void_p] * 5),
+    "tvm_verifier_stir_answers_batch": (C.c_int32, [C.c_void_p, C.c_uint32] + [C.c_void_p] * 12),
+    "tvm_verifier_deep_values_batch": (C.c_int32, [C.c_void_p, C.c_uint32] + [C.c_void_p] * 13),
     "tvm_host_tip5_permutation": (None, [C.c_void_p]),
     "tvm_host_sponge_pad_and_absorb": (None, [C.c_void_p, C.c_void_p, C.c_uint64]),
     "tvm_host_xfe_mul": (None, [C.c_void_p, C.c_void_p, C.c_void_p]),

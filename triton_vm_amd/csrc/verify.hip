@@ -10,66 +10,12 @@
 // the caller, like every other Fiat-Shamir-dependent decision.
 #include "context.h"
 #include "kernels.h"
+#include "verify_kernels.h"
 
 namespace tvm {
 
-TVM_D xfe vf_ld(const u64* p) { return xfe_make(p[0], p[1], p[2]); }
-
-struct VerifyArgs {
-    const u64* main_rows;   // [q][n_main]
-    const u64* aux_rows;    // [q][n_aux][3]
-    const u64* quot_rows;   // [q][5][3]
-    const u64* row_idx;     // [q]
-    const u64* w_ma;        // [n_main + n_aux][3]
-    const u64* small;       // weights_quot[5][3], weights_deep[4][3], ood points[4][3], ood values[4][3]
-    u64 offset, gen;        // low-degree-test domain
-    int n_main, n_aux;
-    u64* out;               // [q][3]
-};
-
-#define VF_BLOCK 256
-__global__ void __launch_bounds__(VF_BLOCK) k_verifier_deep_values(VerifyArgs a) {
-    __shared__ u64 smem[3 * VF_BLOCK];
-    const int tid = threadIdx.x;
-    const u64 j = blockIdx.x;
-    const u64* mrow = a.main_rows + j * (u64)a.n_main;
-    const u64* arow = a.aux_rows + j * (u64)a.n_aux * 3;
-    // linearly_sum_main_and_aux_row (stark.rs:1765-1787)
-    xfe acc = xfe_zero();
-    for (int c = tid; c < a.n_main; c += VF_BLOCK) acc = xfe_add(acc, xfe_mul_bfe(vf_ld(a.w_ma + 3 * c), mrow[c]));
-    for (int c = tid; c < a.n_aux; c += VF_BLOCK) acc = xfe_add(acc, xfe_mul(vf_ld(a.w_ma + 3 * (a.n_main + c)), vf_ld(arow + 3 * c)));
-    // sum over the workgroup
-    smem[tid] = acc.c0, smem[VF_BLOCK + tid] = acc.c1, smem[2 * VF_BLOCK + tid] = acc.c2;
-    __syncthreads();
-    for (int s = VF_BLOCK >> 1; s > 0; s >>= 1) {
-        if (tid < s)
-            for (int k = 0; k < 3; k++) smem[k * VF_BLOCK + tid] = bfe_add(smem[k * VF_BLOCK + tid], smem[k * VF_BLOCK + tid + s]);
-        __syncthreads();
-    }
-    if (tid) return;
-    const xfe ma = xfe_make(smem[0], smem[VF_BLOCK], smem[2 * VF_BLOCK]);
-    const u64* wq = a.small;
-    const u64* wd = a.small + 15;
-    const u64* pts = a.small + 27;
-    const u64* vals = a.small + 39;
-    const u64* q = a.quot_rows + j * 15;
-    // quotient segments: P uses segments 0..3, R segments 1..4 (stark.rs:1700-1717)
-    xfe shared = xfe_zero();
-    for (int k = 1; k < 4; k++) shared = xfe_add(shared, xfe_mul(vf_ld(q + 3 * k), vf_ld(wq + 3 * k)));
-    const xfe for_p = xfe_add(xfe_mul(vf_ld(wq), vf_ld(q)), shared);
-    const xfe for_r = xfe_add(xfe_mul(vf_ld(wq + 12), vf_ld(q + 12)), shared);
-    // deep_update (stark.rs:2096-2103): (value - ood value) / (domain point - ood point)
-    const u64 x = bfe_mul(a.offset, bfe_pow(a.gen, a.row_idx[j]));
-    const xfe elems[4] = {ma, ma, for_p, for_r};
-    xfe total = xfe_zero();
-    for (int k = 0; k < 4; k++) {
-        const xfe num = xfe_sub(elems[k], vf_ld(vals + 3 * k));
-        const xfe den = xfe_bfe_minus(x, vf_ld(pts + 3 * k));
-        total = xfe_add(total, xfe_mul(vf_ld(wd + 3 * k), xfe_mul(num, xfe_inv(den))));
-    }
-    u64* o = a.out + 3 * j;
-    o[0] = total.c0, o[1] = total.c1, o[2] = total.c2;
-}
+// the kernel's body, VerifyArgs and VF_BLOCK: verify_kernels.h (shared with verify_batch.hip)
+__global__ void __launch_bounds__(VF_BLOCK) k_verifier_deep_values(VerifyArgs a) { verifier_deep_values_row(a, blockIdx.x); }
 
 // rows [n][w] row-major -> the row-block-major layout the row-hashing kernel reads
 __global__ void k_rows_to_table(const u64* __restrict__ rows, u64 n, int W, u64* __restrict__ table) {

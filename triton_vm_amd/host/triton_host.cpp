@@ -1198,11 +1198,11 @@ std::vector<u64> prove_execution(const Context& c, const StarkParameters& p, con
 
 }  // namespace triton_vm
 
-static std::atomic<uint64_t> g_options[10] = {{0}, {0}, {0}, {0}, {0}, {0}, {0}, {0}, {0}, {0}};   // indexed by TVMH_OPTION_*
+static std::atomic<uint64_t> g_options[11] = {{0}, {0}, {0}, {0}, {0}, {0}, {0}, {0}, {0}, {0}, {0}};   // indexed by TVMH_OPTION_*
 extern "C" void tvmh_set_option(uint32_t option, uint64_t value) {
-    if (option >= 1 && option <= 9) g_options[option].store(value);
+    if (option >= 1 && option <= 10) g_options[option].store(value);
 }
-extern "C" uint64_t tvmh_get_option(uint32_t option) { return option >= 1 && option <= 9 ? g_options[option].load() : 0; }
+extern "C" uint64_t tvmh_get_option(uint32_t option) { return option >= 1 && option <= 10 ? g_options[option].load() : 0; }
 
 extern "C" int32_t tvmh_prove(tvm_ctx* ctx, uint32_t log2_padded_height, uint64_t num_trace_randomizers,
                               uint64_t num_collinearity_checks, uint32_t log2_expansion, const uint64_t* d_main_trace,

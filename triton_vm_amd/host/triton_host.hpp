@@ -330,6 +330,30 @@ extern "C" int32_t tvmh_verify(tvm_ctx* ctx, const uint64_t* h_proof, uint64_t p
                                const uint64_t* h_public_output, uint64_t n_public_output, uint32_t security_level,
                                uint32_t log2_expansion, uint32_t ldt_choice, uint32_t* verdict, uint64_t* h_indices,
                                uint64_t indices_capacity, uint64_t* n_indices, double* stage_ms, char* error, uint64_t error_capacity);
+// Verifier::verify for MANY proofs per call (verify_batch.cpp): the host walks every job's transcript first, then the device work of all
+// jobs runs stage by stage -- one round trip per stage per chunk of jobs instead of one per stage per proof.  One context, one stream, no
+// host threads.  A job is what tvmh_verify takes for one proof; jobs may differ in height, parameters and low-degree test.
+typedef struct tvmh_verify_job {
+    const uint64_t* h_proof;          uint64_t proof_words;
+    const uint64_t* h_program_digest; /* 5 words, null = zeros */
+    uint32_t version;
+    const uint64_t* h_public_input;   uint64_t n_public_input;
+    const uint64_t* h_public_output;  uint64_t n_public_output;
+    uint32_t security_level, log2_expansion, ldt_choice;   /* as tvmh_verify takes them */
+} tvmh_verify_job;
+// verdicts[i], the revealed indices of job i and their number are exactly what tvmh_verify answers for job i alone, whatever else is in the
+// batch and in whatever order: a job's verdict is its failing check that comes first in Verifier::verify's order (verify_batch.cpp's head).
+// A rejection is a verdict; TVM_ERR_* is for bad arguments and device failures only.  A null proof with a non-zero length, a null claim
+// array with a non-zero length or a parameter outside tvmh_verify's ranges fails the call before any work is done and before any verdict
+// is written; the message names the job.  n_jobs == 0 is TVM_OK.  The indices of an accepted job i go to h_indices + i * indices_stride
+// where indices_stride suffices (0 = none wanted; nothing is ever written past a job's stride); n_indices[i] (n_indices may be null) is
+// their number, 0 for a rejected job.  stage_ms: null, or six doubles as tvmh_verify's, summed over the batch (the host's walk of the
+// low-degree tests and the rows counts as "low-degree test").
+// The batch is processed in chunks of TVMH_OPTION_VERIFY_BATCH_CHUNK jobs (below): a chunk's proofs, trees and rows are staged together.
+extern "C" int32_t tvmh_verify_batch(tvm_ctx* ctx, const tvmh_verify_job* jobs, uint64_t n_jobs, uint32_t* verdicts /* [n_jobs] */,
+                                     uint64_t* h_indices, uint64_t indices_stride /* words per job; 0 = none wanted */,
+                                     uint64_t* n_indices /* [n_jobs], may be null */,
+                                     double* stage_ms /* null or six doubles, summed over the batch */, char* error, uint64_t error_capacity);
 // Proof::padded_height: *verdict 0 and the height, or the decoding verdict
 extern "C" int32_t tvmh_proof_padded_height(const uint64_t* h_proof, uint64_t proof_words, uint32_t* verdict, uint64_t* padded_height);
 extern "C" const char* tvmh_verdict_name(uint32_t verdict);
@@ -571,6 +595,10 @@ extern "C" uint64_t tvmh_device_middle_proofs(void);
 #define TVMH_OPTION_DEVICE_FRONT 9
 // how many proofs of this process took that path so far (a proof it does not apply to is not counted)
 extern "C" uint64_t tvmh_device_front_proofs(void);
+// TVMH_OPTION_VERIFY_BATCH_CHUNK = k > 0: tvmh_verify_batch processes its jobs in chunks of k; 0 (the default) restores the default of 16
+// jobs per chunk.  Whatever the option says, a chunk ends after 102 jobs (40 trees per job at the most, TVM_VERIFIER_MAX_TREES per
+// tvm_verifier_merkle_roots call) and once it holds 2^21 proof words (16 MiB).  Verdicts and indices do not depend on it.
+#define TVMH_OPTION_VERIFY_BATCH_CHUNK 10
 extern "C" void tvmh_set_option(uint32_t option, uint64_t value);
 extern "C" uint64_t tvmh_get_option(uint32_t option);
 

@@ -18,6 +18,7 @@
 
 #include "host_internal.hpp"
 #include "triton_host.hpp"
+#include "verifier_internal.hpp"
 
 namespace triton_vm {
 
@@ -50,28 +51,9 @@ const char* verdict_name(uint32_t verdict) {
     return "unknown verdict";
 }
 
+using namespace verifier_detail;   // the items, the walk, the front and the inclusion jobs: verifier_internal.hpp (shared with verify_batch.cpp)
 namespace {
-[[noreturn]] void reject(uint32_t verdict) { throw VerificationFailure(verdict); }
-u64 from_mont(u64 w) { return mont_mul(w, 1); }
-u64 bfe_sub(u64 a, u64 b) { return (u64)(((unsigned __int128)(a % P) + P - (b % P)) % P); }
-Xfe xfe_sub(const Xfe& a, const Xfe& b) { return Xfe{{bfe_sub(a.c[0], b.c[0]), bfe_sub(a.c[1], b.c[1]), bfe_sub(a.c[2], b.c[2])}}; }
-Xfe xfe_inv(const Xfe& a) {
-    Xfe o;
-    tvm_host_xfe_inv(a.c, o.c);
-    return o;
-}
-Xfe lift(u64 b) { return Xfe{{b, 0, 0}}; }
-Xfe xfe_at(const u64* w) { return Xfe{{w[0], w[1], w[2]}}; }
-bool xfe_eq(const Xfe& a, const Xfe& b) { return a.c[0] == b.c[0] && a.c[1] == b.c[1] && a.c[2] == b.c[2]; }
-const Xfe ZERO{{0, 0, 0}};
 constexpr int STAGE_LDT = Verifier::STAGE_LDT, STAGE_INCLUSION = Verifier::STAGE_INCLUSION, STAGE_ROW_DIGESTS = Verifier::STAGE_ROW_DIGESTS;
-
-// proof_item.rs:96-150 in declaration order (= discriminant)
-enum { MERKLE_ROOT, LOG2_PADDED_HEIGHT, OOD_MAIN_ROW, OOD_AUX_ROW, OOD_QUOTIENT_SEGMENTS, POLYNOMIAL, STIR_OOD_VALUES, AUTH_STRUCTURE,
-       MAIN_ROWS, AUX_ROWS, QUOTIENT_SEGMENT_ELEMENTS, FRI_CODEWORD, FRI_RESPONSE, STIR_RESPONSE, NUM_VARIANTS };
-// > 0: statically sized, that many words; < 0: Vec of that many words per element; 0: polynomial or response
-const int64_t PAYLOAD[NUM_VARIANTS] = {5, 1, 379 * 3, 91 * 3, 4 * 3, 0, -3, -5, -379, -273, -15, -3, 0, 0};
-const bool FIAT_SHAMIR[NUM_VARIANTS] = {true, true, true, true, true, true, true, false, false, false, false, false, false, false};
 }  // namespace
 
 // ------------------------------------------------------------------------------------------------ ProofStream::try_from(&Proof)
@@ -162,80 +144,65 @@ u64 proof_padded_height(const u64* words, u64 n) {
 }
 
 // ------------------------------------------------------------------------------------------------ Verifier::verify
-namespace {
-struct Inclusion {   // one deferred MerkleTreeInclusionProof::verify
-    u64 n_leaves;
-    std::vector<u64> idx, digests, rows;   // digests [q][5], or rows [q][row_words] still to be hashed
-    u64 row_words;
-    const u64 *auth, *root;
-    u64 n_auth;
-    uint32_t verdict;
-};
+namespace verifier_detail {
+std::vector<char> run_inclusion_jobs(const Context& c, const std::vector<Inclusion*>& inclusions, const std::function<void(int)>& lap) {
+    lap(STAGE_LDT);
+    std::map<u64, std::vector<size_t>> by_width;
+    for (size_t j = 0; j < inclusions.size(); j++)
+        if (inclusions[j]->row_words && !inclusions[j]->idx.empty()) by_width[inclusions[j]->row_words].push_back(j);
+    for (const auto& group : by_width) {
+        std::vector<u64> rows;
+        for (size_t j : group.second) rows.insert(rows.end(), inclusions[j]->rows.begin(), inclusions[j]->rows.end());
+        std::vector<u64> digests(rows.size() / group.first * 5);
+        c.check(tvm_verifier_row_digests(c.raw(), rows.data(), rows.size() / group.first, group.first, digests.data()), "tvm_verifier_row_digests");
+        size_t at = 0;
+        for (size_t j : group.second) {
+            inclusions[j]->digests.assign(digests.begin() + at, digests.begin() + at + 5 * inclusions[j]->idx.size());
+            at += 5 * inclusions[j]->idx.size();
+        }
+    }
+    lap(STAGE_ROW_DIGESTS);
+    const size_t n = inclusions.size();
+    std::vector<u64> n_leaves(n), n_idx(n), n_auth(n), roots(5 * n);
+    std::vector<const u64*> idx(n), leaves(n), auth(n);
+    std::vector<uint32_t> flags(n);
+    for (size_t j = 0; j < n; j++) {
+        const Inclusion& t = *inclusions[j];
+        n_leaves[j] = t.n_leaves, n_idx[j] = t.idx.size(), n_auth[j] = t.n_auth;
+        idx[j] = t.idx.data(), leaves[j] = t.digests.data(), auth[j] = t.auth;
+    }
+    c.check(tvm_verifier_merkle_roots(c.raw(), (uint32_t)n, n_leaves.data(), n_idx.data(), idx.data(), leaves.data(), n_auth.data(),
+                                      auth.data(), roots.data(), flags.data()), "tvm_verifier_merkle_roots");
+    lap(STAGE_INCLUSION);
+    std::vector<char> failed(n);
+    for (size_t j = 0; j < n; j++) failed[j] = flags[j] || std::memcmp(&roots[5 * j], inclusions[j]->root, 5 * sizeof(u64));
+    return failed;
+}
+}  // namespace verifier_detail
 
-struct Run {
+namespace {
+struct Run : Walk {
     const Context& c;
-    const u64* words;
-    std::vector<DecodedItem> items;
-    size_t next = 0;
-    ProofStream sponge;
     std::vector<Inclusion> inclusions;
     double* ms;
     std::chrono::steady_clock::time_point mark = std::chrono::steady_clock::now();
+    Run(const Context& c_, const u64* words_, double* ms_) : Walk(words_), c(c_), ms(ms_) {}
 
     void lap(int stage) {
         const auto now = std::chrono::steady_clock::now();
         ms[stage] += std::chrono::duration<double, std::milli>(now - mark).count();
         mark = now;
     }
-    const DecodedItem& dequeue(int variant) {   // ProofStream::dequeue (proof_stream.rs:62-72) + the try_into_* of proof_item.rs
-        if (next >= items.size()) reject(VERDICT_PROOF_STREAM_ERROR);   // EmptyQueue
-        const DecodedItem& it = items[next++];
-        if (it.variant != variant) reject(VERDICT_PROOF_STREAM_ERROR);   // UnexpectedItem
-        // the decoder accepts canonical encodings only: the item's words in the proof ARE its encoding
-        if (FIAT_SHAMIR[variant]) sponge.alter_fiat_shamir_state_with(std::vector<u64>(words + it.at, words + it.at + it.size));
-        return it;
-    }
-    const u64* payload(const DecodedItem& it) const { return words + it.payload_at; }
-    Xfe sample() { return sponge.sample_scalars(1)[0]; }
-
     // all queued inclusion jobs: the row digests (one call per row width), then ONE tvm_verifier_merkle_roots
     void flush() {
         if (inclusions.empty()) return;
         std::vector<Inclusion> jobs;
         jobs.swap(inclusions);   // (a failing job leaves nothing queued: flush() runs again when the failure passes verify()'s handler)
-        run_inclusions(jobs);
-    }
-    void run_inclusions(std::vector<Inclusion>& inclusions) {
-        lap(STAGE_LDT);
-        std::map<u64, std::vector<size_t>> by_width;
-        for (size_t j = 0; j < inclusions.size(); j++)
-            if (inclusions[j].row_words && !inclusions[j].idx.empty()) by_width[inclusions[j].row_words].push_back(j);
-        for (const auto& group : by_width) {
-            std::vector<u64> rows;
-            for (size_t j : group.second) rows.insert(rows.end(), inclusions[j].rows.begin(), inclusions[j].rows.end());
-            std::vector<u64> digests(rows.size() / group.first * 5);
-            c.check(tvm_verifier_row_digests(c.raw(), rows.data(), rows.size() / group.first, group.first, digests.data()), "tvm_verifier_row_digests");
-            size_t at = 0;
-            for (size_t j : group.second) {
-                inclusions[j].digests.assign(digests.begin() + at, digests.begin() + at + 5 * inclusions[j].idx.size());
-                at += 5 * inclusions[j].idx.size();
-            }
-        }
-        lap(STAGE_ROW_DIGESTS);
-        const size_t n = inclusions.size();
-        std::vector<u64> n_leaves(n), n_idx(n), n_auth(n), roots(5 * n);
-        std::vector<const u64*> idx(n), leaves(n), auth(n);
-        std::vector<uint32_t> flags(n);
-        for (size_t j = 0; j < n; j++) {
-            const Inclusion& t = inclusions[j];
-            n_leaves[j] = t.n_leaves, n_idx[j] = t.idx.size(), n_auth[j] = t.n_auth;
-            idx[j] = t.idx.data(), leaves[j] = t.digests.data(), auth[j] = t.auth;
-        }
-        c.check(tvm_verifier_merkle_roots(c.raw(), (uint32_t)n, n_leaves.data(), n_idx.data(), idx.data(), leaves.data(), n_auth.data(),
-                                          auth.data(), roots.data(), flags.data()), "tvm_verifier_merkle_roots");
-        lap(STAGE_INCLUSION);
-        for (size_t j = 0; j < n; j++)
-            if (flags[j] || std::memcmp(&roots[5 * j], inclusions[j].root, 5 * sizeof(u64))) reject(inclusions[j].verdict);
+        std::vector<Inclusion*> refs;
+        for (Inclusion& t : jobs) refs.push_back(&t);
+        const std::vector<char> failed = run_inclusion_jobs(c, refs, [this](int stage) { lap(stage); });
+        for (size_t j = 0; j < jobs.size(); j++)
+            if (failed[j]) reject(jobs[j].verdict);
     }
 };
 
@@ -415,9 +382,81 @@ LdtResult stir_verify(Run& run, const Stir& stir) {
 }
 }  // namespace
 
+namespace verifier_detail {
+Front walk_front(const Context& c, Walk& walk, const Claim& claim, unsigned security_level, unsigned log2_expansion, unsigned ldt_choice) {
+    Front f;
+    walk.sponge.alter_fiat_shamir_state_with(claim.encode());
+    const u64 log2_padded_height = from_mont(*walk.payload(walk.dequeue(LOG2_PADDED_HEIGHT)));
+    if (log2_padded_height >= 32) reject(VERDICT_LOG2_PADDED_HEIGHT_TOO_LARGE);
+    f.use_stir = ldt_choice == 2 ? log2_padded_height >= 16 : ldt_choice == 1;   // Stark::ldt (stark.rs:1944-1951)
+    StarkParameters& p = f.p;
+    try {
+        p = stark_parameters((unsigned)log2_padded_height, security_level, log2_expansion, f.use_stir);
+    } catch (const Error&) {   // a height this host derives no parameters for (a domain beyond 2^32 points)
+        reject(VERDICT_UNSUPPORTED_PARAMETERS);
+    }
+
+    // Fiat-Shamir 1 (stark.rs:1418-1437)
+    f.main_root = walk.payload(walk.dequeue(MERKLE_ROOT));
+    const std::vector<Xfe> challenges = derive_challenges(walk.sponge.sample_scalars(NUM_SAMPLED_CHALLENGES), claim);
+    f.aux_root = walk.payload(walk.dequeue(MERKLE_ROOT));
+    const std::vector<Xfe> quotient_weights = xfe_powers(walk.sample(), 0, TVM_NUM_QUOTIENT_WEIGHTS);
+    f.quot_root = walk.payload(walk.dequeue(MERKLE_ROOT));
+
+    // the out-of-domain rows and the quotient value they imply (stark.rs:1439-1539)
+    const Xfe alpha = walk.sample();
+    const u64 zeta = to_mont(3);   // Stark::ZETA, stark.rs:1801
+    const Xfe alpha_next = xfe_scale(alpha, p.trace.generator), alpha_zeta = xfe_scale(alpha, zeta);
+    const Xfe a4 = xfe_powers(alpha, 4, 1)[0], za4 = xfe_powers(alpha_zeta, 4, 1)[0];
+    const u64* main_cur = walk.payload(walk.dequeue(OOD_MAIN_ROW));
+    const u64* aux_cur = walk.payload(walk.dequeue(OOD_AUX_ROW));
+    const u64* main_next = walk.payload(walk.dequeue(OOD_MAIN_ROW));
+    const u64* aux_next = walk.payload(walk.dequeue(OOD_AUX_ROW));
+    const u64* seg_p = walk.payload(walk.dequeue(OOD_QUOTIENT_SEGMENTS));
+    const u64* seg_r = walk.payload(walk.dequeue(OOD_QUOTIENT_SEGMENTS));
+    std::vector<Xfe> constraints(TVM_NUM_QUOTIENT_WEIGHTS);
+    c.check(tvm_host_air_constraints(main_cur, aux_cur, main_next, aux_next, challenges[0].c, constraints[0].c), "tvm_host_air_constraints");
+    const Xfe one = lift(to_mont(1));
+    const Xfe consistency_inv = xfe_inv(xfe_sub(xfe_powers(alpha, p.trace.length, 1)[0], one));
+    const Xfe except_last = xfe_sub(alpha, lift(mont_pow(p.trace.generator, P - 2)));
+    // initial, consistency, transition, terminal (stark.rs:1493-1499)
+    const std::pair<unsigned, Xfe> zerofier_inverse[4] = {{81, xfe_inv(xfe_sub(alpha, one))}, {97, consistency_inv},
+                                                          {403, xfe_mul(except_last, consistency_inv)}, {23, xfe_inv(except_last)}};
+    Xfe ood_quotient = ZERO;
+    unsigned k = 0;
+    for (const auto& section : zerofier_inverse)
+        for (unsigned i = 0; i < section.first; i++, k++)
+            ood_quotient = xfe_add(ood_quotient, xfe_mul(quotient_weights[k], xfe_mul(constraints[k], section.second)));
+    const std::vector<Xfe> alpha_powers = xfe_powers(alpha, 0, 4), alpha_zeta_powers = xfe_powers(alpha_zeta, 0, 4);
+    Xfe derandomized = ZERO;
+    for (int i = 0; i < 4; i++) derandomized = xfe_add(derandomized, xfe_mul(alpha_powers[i], xfe_at(seg_p + 3 * i)));
+    for (int i = 0; i < 4; i++) derandomized = xfe_add(derandomized, xfe_mul(alpha_zeta_powers[i], xfe_at(seg_r + 3 * i)));
+    if (!xfe_eq(ood_quotient, derandomized)) reject(VERDICT_OUT_OF_DOMAIN_QUOTIENT_VALUE_MISMATCH);
+
+    // Fiat-Shamir 2 and the out-of-domain sums (stark.rs:1541-1575)
+    const std::vector<Xfe> iw = walk.sponge.sample_scalars(3);
+    f.w_ma = xfe_powers(iw[0], 0, NUM_MAIN + NUM_AUX), f.w_q = xfe_powers(iw[1], 0, 5), f.w_d = xfe_powers(iw[2], 0, 4);
+    const std::vector<Xfe>&w_ma = f.w_ma, &w_q = f.w_q;
+    auto linear_sum = [&](const u64* m, const u64* a) {
+        Xfe acc = ZERO;
+        for (u64 i = 0; i < NUM_MAIN; i++) acc = xfe_add(acc, xfe_mul(w_ma[i], xfe_at(m + 3 * i)));
+        for (u64 i = 0; i < NUM_AUX; i++) acc = xfe_add(acc, xfe_mul(w_ma[NUM_MAIN + i], xfe_at(a + 3 * i)));
+        return acc;
+    };
+    Xfe* ood_values = f.ood_values;
+    ood_values[0] = linear_sum(main_cur, aux_cur), ood_values[1] = linear_sum(main_next, aux_next), ood_values[2] = ood_values[3] = ZERO;
+    for (int i = 0; i < 4; i++) {
+        ood_values[2] = xfe_add(ood_values[2], xfe_mul(xfe_at(seg_p + 3 * i), w_q[i]));
+        ood_values[3] = xfe_add(ood_values[3], xfe_mul(xfe_at(seg_r + 3 * i), w_q[i + 1]));
+    }
+    f.ood_points[0] = alpha, f.ood_points[1] = alpha_next, f.ood_points[2] = a4, f.ood_points[3] = za4;
+    return f;
+}
+}  // namespace verifier_detail
+
 std::vector<u64> Verifier::verify(const Claim& claim, const u64* proof_words, u64 n_words) {
     std::fill(stage_ms, stage_ms + NUM_STAGES, 0.0);
-    Run run{c_, proof_words, {}, 0, {}, {}, stage_ms};
+    Run run(c_, proof_words, stage_ms);
     try {
         run.items = decode_proof(proof_words, n_words);
     } catch (const VerificationFailure&) {
@@ -426,73 +465,13 @@ std::vector<u64> Verifier::verify(const Claim& claim, const u64* proof_words, u6
     }
     run.lap(STAGE_DECODE);
     try {
-        run.sponge.alter_fiat_shamir_state_with(claim.encode());
-        const u64 log2_padded_height = from_mont(*run.payload(run.dequeue(LOG2_PADDED_HEIGHT)));
-        if (log2_padded_height >= 32) reject(VERDICT_LOG2_PADDED_HEIGHT_TOO_LARGE);
-        const bool use_stir = ldt_choice_ == 2 ? log2_padded_height >= 16 : ldt_choice_ == 1;   // Stark::ldt (stark.rs:1944-1951)
-        StarkParameters p(0);
-        try {
-            p = stark_parameters((unsigned)log2_padded_height, security_level_, log2_expansion_, use_stir);
-        } catch (const Error&) {   // a height this host derives no parameters for (a domain beyond 2^32 points)
-            reject(VERDICT_UNSUPPORTED_PARAMETERS);
-        }
+        const Front front = walk_front(c_, run, claim, security_level_, log2_expansion_, ldt_choice_);
+        const StarkParameters& p = front.p;
         const u64 checks = p.num_collinearity_checks;
-
-        // Fiat-Shamir 1 (stark.rs:1418-1437)
-        const u64* main_root = run.payload(run.dequeue(MERKLE_ROOT));
-        const std::vector<Xfe> challenges = derive_challenges(run.sponge.sample_scalars(NUM_SAMPLED_CHALLENGES), claim);
-        const u64* aux_root = run.payload(run.dequeue(MERKLE_ROOT));
-        const std::vector<Xfe> quotient_weights = xfe_powers(run.sample(), 0, TVM_NUM_QUOTIENT_WEIGHTS);
-        const u64* quot_root = run.payload(run.dequeue(MERKLE_ROOT));
-
-        // the out-of-domain rows and the quotient value they imply (stark.rs:1439-1539)
-        const Xfe alpha = run.sample();
-        const u64 zeta = to_mont(3);   // Stark::ZETA, stark.rs:1801
-        const Xfe alpha_next = xfe_scale(alpha, p.trace.generator), alpha_zeta = xfe_scale(alpha, zeta);
-        const Xfe a4 = xfe_powers(alpha, 4, 1)[0], za4 = xfe_powers(alpha_zeta, 4, 1)[0];
-        const u64* main_cur = run.payload(run.dequeue(OOD_MAIN_ROW));
-        const u64* aux_cur = run.payload(run.dequeue(OOD_AUX_ROW));
-        const u64* main_next = run.payload(run.dequeue(OOD_MAIN_ROW));
-        const u64* aux_next = run.payload(run.dequeue(OOD_AUX_ROW));
-        const u64* seg_p = run.payload(run.dequeue(OOD_QUOTIENT_SEGMENTS));
-        const u64* seg_r = run.payload(run.dequeue(OOD_QUOTIENT_SEGMENTS));
-        std::vector<Xfe> constraints(TVM_NUM_QUOTIENT_WEIGHTS);
-        c_.check(tvm_host_air_constraints(main_cur, aux_cur, main_next, aux_next, challenges[0].c, constraints[0].c), "tvm_host_air_constraints");
-        const Xfe one = lift(to_mont(1));
-        const Xfe consistency_inv = xfe_inv(xfe_sub(xfe_powers(alpha, p.trace.length, 1)[0], one));
-        const Xfe except_last = xfe_sub(alpha, lift(mont_pow(p.trace.generator, P - 2)));
-        // initial, consistency, transition, terminal (stark.rs:1493-1499)
-        const std::pair<unsigned, Xfe> zerofier_inverse[4] = {{81, xfe_inv(xfe_sub(alpha, one))}, {97, consistency_inv},
-                                                              {403, xfe_mul(except_last, consistency_inv)}, {23, xfe_inv(except_last)}};
-        Xfe ood_quotient = ZERO;
-        unsigned k = 0;
-        for (const auto& section : zerofier_inverse)
-            for (unsigned i = 0; i < section.first; i++, k++)
-                ood_quotient = xfe_add(ood_quotient, xfe_mul(quotient_weights[k], xfe_mul(constraints[k], section.second)));
-        const std::vector<Xfe> alpha_powers = xfe_powers(alpha, 0, 4), alpha_zeta_powers = xfe_powers(alpha_zeta, 0, 4);
-        Xfe derandomized = ZERO;
-        for (int i = 0; i < 4; i++) derandomized = xfe_add(derandomized, xfe_mul(alpha_powers[i], xfe_at(seg_p + 3 * i)));
-        for (int i = 0; i < 4; i++) derandomized = xfe_add(derandomized, xfe_mul(alpha_zeta_powers[i], xfe_at(seg_r + 3 * i)));
-        if (!xfe_eq(ood_quotient, derandomized)) reject(VERDICT_OUT_OF_DOMAIN_QUOTIENT_VALUE_MISMATCH);
-
-        // Fiat-Shamir 2 and the out-of-domain sums (stark.rs:1541-1575)
-        const std::vector<Xfe> iw = run.sponge.sample_scalars(3);
-        const std::vector<Xfe> w_ma = xfe_powers(iw[0], 0, NUM_MAIN + NUM_AUX), w_q = xfe_powers(iw[1], 0, 5), w_d = xfe_powers(iw[2], 0, 4);
-        auto linear_sum = [&](const u64* m, const u64* a) {
-            Xfe acc = ZERO;
-            for (u64 i = 0; i < NUM_MAIN; i++) acc = xfe_add(acc, xfe_mul(w_ma[i], xfe_at(m + 3 * i)));
-            for (u64 i = 0; i < NUM_AUX; i++) acc = xfe_add(acc, xfe_mul(w_ma[NUM_MAIN + i], xfe_at(a + 3 * i)));
-            return acc;
-        };
-        Xfe ood_values[4] = {linear_sum(main_cur, aux_cur), linear_sum(main_next, aux_next), ZERO, ZERO};
-        for (int i = 0; i < 4; i++) {
-            ood_values[2] = xfe_add(ood_values[2], xfe_mul(xfe_at(seg_p + 3 * i), w_q[i]));
-            ood_values[3] = xfe_add(ood_values[3], xfe_mul(xfe_at(seg_r + 3 * i), w_q[i + 1]));
-        }
         run.lap(STAGE_TRANSCRIPT_AIR);
 
         // the low-degree test (stark.rs:1577-1590)
-        const LdtResult ldt = use_stir ? stir_verify(run, p.stir) : fri_verify(run, p);
+        const LdtResult ldt = front.use_stir ? stir_verify(run, p.stir) : fri_verify(run, p);
         if (ldt.indices.size() != checks || ldt.revealed.size() != 3 * checks) reject(VERDICT_INCORRECT_NUMBER_OF_ROW_INDICES);
         run.lap(STAGE_LDT);
 
@@ -505,17 +484,17 @@ std::vector<u64> Verifier::verify(const Claim& claim, const u64* proof_words, u6
                                                width, run.payload(auth), root, auth.payload_words / 5, wrong_path});
             return run.payload(rows);
         };
-        const u64* main_rows = rows_of(MAIN_ROWS, NUM_MAIN, main_root, VERDICT_INCORRECT_NUMBER_OF_MAIN_ROWS, VERDICT_MAIN_CODEWORD_AUTHENTICATION_FAILURE);
-        const u64* aux_rows = rows_of(AUX_ROWS, NUM_AUX * 3, aux_root, VERDICT_INCORRECT_NUMBER_OF_AUX_ROWS, VERDICT_AUX_CODEWORD_AUTHENTICATION_FAILURE);
-        const u64* quot_rows = rows_of(QUOTIENT_SEGMENT_ELEMENTS, 15, quot_root, VERDICT_INCORRECT_NUMBER_OF_QUOTIENT_SEGMENT_ELEMENTS,
+        const u64* main_rows = rows_of(MAIN_ROWS, NUM_MAIN, front.main_root, VERDICT_INCORRECT_NUMBER_OF_MAIN_ROWS, VERDICT_MAIN_CODEWORD_AUTHENTICATION_FAILURE);
+        const u64* aux_rows = rows_of(AUX_ROWS, NUM_AUX * 3, front.aux_root, VERDICT_INCORRECT_NUMBER_OF_AUX_ROWS, VERDICT_AUX_CODEWORD_AUTHENTICATION_FAILURE);
+        const u64* quot_rows = rows_of(QUOTIENT_SEGMENT_ELEMENTS, 15, front.quot_root, VERDICT_INCORRECT_NUMBER_OF_QUOTIENT_SEGMENT_ELEMENTS,
                                        VERDICT_QUOTIENT_CODEWORD_AUTHENTICATION_FAILURE);
         run.flush();
 
         // the combination codeword at the revealed rows, on the device (stark.rs:1674-1755)
-        const Xfe ood_points[4] = {alpha, alpha_next, a4, za4};
         std::vector<u64> want(3 * checks);
-        c_.check(tvm_verifier_deep_values(c_.raw(), main_rows, aux_rows, quot_rows, ldt.indices.data(), checks, p.ldt.c(), w_ma[0].c, w_q[0].c,
-                                          w_d[0].c, ood_points[0].c, ood_values[0].c, want.data()), "tvm_verifier_deep_values");
+        c_.check(tvm_verifier_deep_values(c_.raw(), main_rows, aux_rows, quot_rows, ldt.indices.data(), checks, p.ldt.c(), front.w_ma[0].c,
+                                          front.w_q[0].c, front.w_d[0].c, front.ood_points[0].c, front.ood_values[0].c, want.data()),
+                 "tvm_verifier_deep_values");
         run.lap(STAGE_DEEP_VALUES);
         if (want != ldt.revealed) reject(VERDICT_COMBINATION_CODEWORD_MISMATCH);
         if (run.next != run.items.size()) reject(VERDICT_SUPERFLUOUS_PROOF_ITEMS);

@@ -41,6 +41,9 @@ def load_host_library(backend_path=None, out=None):
     lib.tvmh_verify.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64,
                                 C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64),
                                 C.c_void_p, C.c_char_p, C.c_uint64]
+    lib.tvmh_verify_batch.restype = C.c_int32
+    lib.tvmh_verify_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_char_p,
+                                      C.c_uint64]
     lib.tvmh_proof_padded_height.restype = C.c_int32
     lib.tvmh_proof_padded_height.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]
     lib.tvmh_verdict_name.restype = C.c_char_p
@@ -77,6 +80,7 @@ OPTION_DEVICE_TAIL = 6   # single-GPU FRI proofs: the query phase and the trace 
 OPTION_DEVICE_STIR = 7   # Stir::prove: all rounds in one call with the sponge on the device (stir_rounds.py)
 OPTION_DEVICE_MIDDLE = 8   # single-GPU proofs: the quotient root, the out-of-domain rows, the combinations and DEEP in one device round trip (proof_middle.py)
 OPTION_DEVICE_FRONT = 9    # single-GPU proofs: main root to the segment table queued without a wait, challenges and quotient weights made on the device (proof_front.py)
+OPTION_VERIFY_BATCH_CHUNK = 10   # tvmh_verify_batch: jobs per chunk (0: the default, 16)
 
 
 class host_option:
@@ -389,6 +393,54 @@ def verify(ctx, host_lib, claim, proof_words, security_level=160, log2_expansion
     if verdict != 0:
         raise VerificationError(name)
     return indices
+
+
+class VerifyJob(C.Structure):
+    """struct tvmh_verify_job"""
+    _fields_ = [("h_proof", C.c_void_p), ("proof_words", C.c_uint64), ("h_program_digest", C.c_void_p), ("version", C.c_uint32),
+                ("h_public_input", C.c_void_p), ("n_public_input", C.c_uint64), ("h_public_output", C.c_void_p), ("n_public_output", C.c_uint64),
+                ("security_level", C.c_uint32), ("log2_expansion", C.c_uint32), ("ldt_choice", C.c_uint32)]
+
+
+def verify_job(claim, proof_words, security_level=160, log2_expansion=2, ldt=None):
+    """one job of verify_batch: (claim, proof words, parameters as verify takes them); ldt may also be the number tvmh_verify takes"""
+    return (claim, proof_words, security_level, log2_expansion, ldt)
+
+
+def verify_batch_verdicts(ctx, host_lib, jobs, indices_stride=1 << 12):
+    """tvmh_verify_batch as it is.  jobs: [verify_job(...)] -> (status, error text, [verdict code], [indices of job i, [] unless accepted
+    and within the stride], [number of indices], {stage: ms summed over the batch}); no exception for a rejection.  A proof given as None
+    is passed as a null pointer with the length 1 (an argument error)."""
+    n = len(jobs)
+    array, keep = (VerifyJob * max(n, 1))(), []
+    for i, (claim, proof_words, security_level, log2_expansion, ldt) in enumerate(jobs):
+        words = None if proof_words is None else np.ascontiguousarray(proof_words, dtype=np.uint64).reshape(-1)
+        digest = np.ascontiguousarray(claim.program_digest, dtype=np.uint64)
+        public_input, output = np.ascontiguousarray(claim.input, dtype=np.uint64), np.ascontiguousarray(claim.output, dtype=np.uint64)
+        keep.append((words, digest, public_input, output))
+        array[i] = VerifyJob(None if words is None else words.ctypes.data, 1 if words is None else words.size, digest.ctypes.data, claim.version,
+                             public_input.ctypes.data, public_input.size, output.ctypes.data, output.size, security_level, log2_expansion,
+                             ldt if isinstance(ldt, int) else {"fri": 0, "stir": 1, None: 2}[ldt])
+    verdicts, counts = np.full(max(n, 1), 0xFFFFFFFF, np.uint32), np.full(max(n, 1), 0xFFFFFFFFFFFFFFFF, np.uint64)
+    indices = np.full((max(n, 1), max(indices_stride, 1)), 0xFFFFFFFFFFFFFFFF, np.uint64)
+    stages, err = np.zeros(len(VERIFY_STAGES), np.float64), C.create_string_buffer(256)
+    rc = host_lib.tvmh_verify_batch(ctx.handle, C.addressof(array), n, verdicts.ctypes.data, indices.ctypes.data if indices_stride else None,
+                                    indices_stride, counts.ctypes.data, stages.ctypes.data, err, len(err))
+    revealed = [[int(v) for v in indices[i, :counts[i]]] if rc == 0 and verdicts[i] == 0 and counts[i] <= indices_stride else [] for i in range(n)]
+    return rc, err.value.decode(), [int(v) for v in verdicts[:n]], revealed, [int(v) for v in counts[:n]], dict(zip(VERIFY_STAGES, stages.tolist()))
+
+
+def verify_batch(ctx, host_lib, jobs):
+    """The C++ host's Verifier::verify for many proofs in one call, the device work shared between them (tvmh_verify_batch,
+    host/verify_batch.cpp).  jobs: [verify_job(claim, proof_words, ...)] -> per job the revealed first-round indices, or the
+    verifier.VerificationError that verify() would raise for it (returned, not raised: a rejected job does not hide the others);
+    raises NativeHostError on a bad argument or a device failure."""
+    from .verifier import VerificationError
+
+    rc, error, verdicts, revealed, _, _ = verify_batch_verdicts(ctx, host_lib, jobs)
+    if rc != 0:
+        raise NativeHostError(rc, f"tvmh_verify_batch failed ({rc}): {error}")
+    return [indices if verdict == 0 else VerificationError(host_lib.tvmh_verdict_name(verdict).decode()) for verdict, indices in zip(verdicts, revealed)]
 
 
 def proof_padded_height(host_lib, proof_words):
